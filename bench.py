@@ -11,11 +11,19 @@ EaBNet.forward -> (B, 2, T, F).  Workload = BASELINE.json configs[1]/[2]
 hand-written HIP path).  Utterances are independent, so N GPUs run N
 independent shards (weak scaling, no data-path collective).
 
-Prints ONE JSON line on rank 0 (see the keys below); `roofline` is measured in
-an instrumented replay (HIP events around every op of the program, on the
-stream the kernels run on) right after the timed region, `cpu_baseline` times
-the oracle (oracle/eabnet_oracle.py, test infrastructure) on the host cores on
-a bounded sample of the same workload.
+Prints ONE JSON line on rank 0 (see the keys below).  A plain run sets up, picks
+the executor (pipelined or one batch at a time, on a short untimed window),
+warms up, times the K steps and prints the headline.  `--dump-outputs DIR`
+writes what the last timed step returned (DIR/enhanced_stft.npy, float32).
+
+`--full` adds everything else, after the timed steps: the one-step-at-a-time
+timing, the in-run equality checks of the executors, the f16x3 mode,
+`roofline` (an instrumented replay: HIP events around every op of the program,
+on the stream the kernels run on), the HBM-side kernels, the single-utterance
+latency, the next rows (post-filter, streaming, host input, training) and
+`cpu_baseline` (the oracle, oracle/eabnet_oracle.py, test infrastructure, on
+the host cores on a bounded sample of the same workload).  The `--no-*` flags
+switch single sections of `--full` off.
 """
 from __future__ import annotations
 
@@ -424,6 +432,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: one-step-at-a-time timing, in-run checks, f16x3 mode, roofline, HBM kernels, "
+                         "single utterance, next rows (post-filter, streaming, host input, training) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the output of the last timed step as DIR/enhanced_stft.npy (float32, (B, 2, T, F) of rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-alt", action="store_true", help="skip the secondary f16x3 measurement")
@@ -435,7 +448,8 @@ def main():
     ap.add_argument("--no-train", action="store_true", help="skip the training-step section of the next rows (BASELINE configs[3])")
     ap.add_argument("--precision", choices=("f32", "f16x3", "bf16"), default="f32",
                     help="MFMA arithmetic of the timed path (DESIGN.md §4.4)")
-    ap.add_argument("--per-op", type=str, default="", help="write the per-op timing table (instrumented replay) here")
+    ap.add_argument("--per-op", type=str, default="",
+                    help="write the per-op timing table (instrumented replay) here; needs --full (or --train)")
     ap.add_argument("--train", action="store_true",
                     help="BASELINE configs[3]: training step (prepare_data, forward, loss, backward, clip, Adam) on the HIP "
                          "training programs, per-GPU batch 6 x 6 s x 8 mics, one flat RCCL gradient all-reduce per step")
@@ -447,6 +461,10 @@ def main():
     ap.add_argument("--train-ddp", action="store_true", help="with --train: wrap in torch DistributedDataParallel (one 64 MB bucket, "
                                                              "gradient_as_bucket_view, static_graph) instead of the flat all-reduce")
     a = ap.parse_args()
+    if a.per_op and not (a.full or a.train):
+        ap.error("--per-op comes from the instrumented replay of --full")
+    if a.dump_outputs and a.train:
+        ap.error("--dump-outputs writes the inference headline's output; it is not available with --train")
 
     rank, world, local = dist.env_rank()
     if world == 1 and a.gpus > 1:
@@ -474,11 +492,16 @@ def main():
         ns = eabnet_amd.stft_compress(wav, N_FFT, HOP, window)
         return net(ns), ns
 
-    def timed_steps(depth: int, warmup: int, steps: int):
+    kept_pipes: dict = {}
+
+    def timed_steps(depth: int, warmup: int, steps: int, keep: bool = False):
         """`steps` passes wave -> STFT -> EaBNet over the resident batch with `depth` of them in flight
         (eabnet_amd.Pipeline; depth 1 = one after the other), bracketed by barrier + synchronize; returns
-        (max-over-ranks seconds, last output)."""
-        pipe = eabnet_amd.Pipeline(net, depth=depth, front_end=(N_FFT, HOP, window))
+        (max-over-ranks seconds, last output).  keep=True: the next call of this depth reuses the pipeline
+        (its replicas' lowered and captured programs)."""
+        pipe = kept_pipes.pop(depth, None) or eabnet_amd.Pipeline(net, depth=depth, front_end=(N_FFT, HOP, window))
+        if keep:
+            kept_pipes[depth] = pipe
         with torch.no_grad():
             if depth > 1 and not _CALIBRATED:
                 pipe.calibrate(wav)                      # untimed: pick streams that actually overlap on this box
@@ -504,19 +527,40 @@ def main():
         per_rank.extend(dist.gather_over_ranks(el, dev))
         return dist.max_over_ranks(el, dev), yy
 
+    def emit(out):
+        if rank == 0:
+            print(json.dumps(out))
+        if is_dist:
+            dist.barrier()
+            torch.distributed.destroy_process_group()
+
     per_rank: list = []                   # elapsed seconds of every rank in the most recent timed region
     depth = max(1, a.pipeline)
+    if depth > 1 and not a.full:
+        # untimed: streams that happen to share a hardware queue do not overlap, and then the plain loop IS the better
+        # executor.  A short window of each picks the one the K steps run on (--full times the K steps both ways instead).
+        probe_pipe = timed_steps(depth, 0, 16, keep=True)[0]
+        probe_seq = timed_steps(1, 2, 16)[0]
+        if probe_seq < probe_pipe:
+            depth = 1
     elapsed, y = timed_steps(depth, a.warmup, a.steps)
+    kept_pipes.clear()
     rank_elapsed = list(per_rank)
-    assert torch.isfinite(y).all()
-    seq_elapsed = timed_steps(1, 2, a.steps)[0] if depth > 1 else elapsed
-    if seq_elapsed < elapsed:
-        # streams that happen to share a hardware queue do not overlap; then the plain loop IS the better executor
-        # and the headline is its (equally complete) timing of the same K steps
-        elapsed, depth, rank_elapsed = seq_elapsed, 1, list(per_rank)
-    with torch.no_grad():
-        y_seq, ns = step()
-    assert torch.equal(y_seq, y), "the pipelined executor must return exactly what net(x) returns"
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: EaBNet's (B, 2, T, F) output of rank 0's batch
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "enhanced_stft.npy"), y.detach().float().cpu().numpy())
+    seq_elapsed = elapsed
+    if a.full:
+        assert torch.isfinite(y).all()
+        seq_elapsed = timed_steps(1, 2, a.steps)[0] if depth > 1 else elapsed
+        if seq_elapsed < elapsed:
+            # streams that happen to share a hardware queue do not overlap; then the plain loop IS the better executor
+            # and the headline is its (equally complete) timing of the same K steps
+            elapsed, depth, rank_elapsed = seq_elapsed, 1, list(per_rank)
+        with torch.no_grad():
+            y_seq, ns = step()
+        assert torch.equal(y_seq, y), "the pipelined executor must return exactly what net(x) returns"
 
     def pipelined_results_all_equal(want, n=8) -> bool:
         """untimed: every one of n pipelined results (not only the last, which runs while the pipeline drains)
@@ -528,7 +572,7 @@ def main():
                 ok = ok and bool(torch.equal(yy, want))
         torch.cuda.synchronize()
         return ok
-    if a.pipeline > 1:             # (--pipeline 1 = the profiling recipe: one batch in flight, nothing pipelined anywhere)
+    if a.full and a.pipeline > 1:  # (--pipeline 1 = the profiling recipe: one batch in flight, nothing pipelined anywhere)
         assert pipelined_results_all_equal(y_seq), "a pipelined result differs from the direct call (f32)"
 
     frames = world * B_PER_GPU * T * a.steps
@@ -542,10 +586,6 @@ def main():
                    "batch_per_gpu": B_PER_GPU, "global_batch": world * B_PER_GPU, "mics": MICS, "frames_per_utt": T,
                    "freq_bins": N_FFT // 2 + 1, "parallelism": f"dp{world} (independent shards, no collective)",
                    "pipeline_depth": depth},
-        "one_step_at_a_time": {"ms_per_step": 1e3 * seq_elapsed / a.steps, "value": frames / seq_elapsed,
-                               "note": "same protocol with a single batch in flight (pipeline depth 1): the latency of "
-                                       "a step; the headline keeps `pipeline_depth` batches in flight on separate HIP "
-                                       "streams (eabnet_amd.Pipeline), results bit-identical"},
         "rtf_per_utterance": elapsed / a.steps / (B_PER_GPU * SECONDS),
         "ranks": {"world_size_seen_by_torch_distributed": torch.distributed.get_world_size() if is_dist else 1,
                   "backend": "nccl (RCCL)" if is_dist else "none (single process)",
@@ -556,9 +596,16 @@ def main():
     # whole path against the fp32 matrix peak (frames/s x FLOP/frame, summed over the ranks' GPUs)
     ms_step = out["ms_per_step"]
     out["whole_path"] = {"achieved_tflops": out["gflop_per_step_algorithmic"] * world / ms_step,
-                         "frac_of_fp32_mfma_peak": out["gflop_per_step_algorithmic"] / ms_step / PEAK_FP32_MFMA_TFLOPS,
-                         "one_step_at_a_time_frac": out["gflop_per_step_algorithmic"]
-                         / out["one_step_at_a_time"]["ms_per_step"] / PEAK_FP32_MFMA_TFLOPS}
+                         "frac_of_fp32_mfma_peak": out["gflop_per_step_algorithmic"] / ms_step / PEAK_FP32_MFMA_TFLOPS}
+    if not a.full:
+        return emit(out)
+
+    out["one_step_at_a_time"] = {"ms_per_step": 1e3 * seq_elapsed / a.steps, "value": frames / seq_elapsed,
+                                 "note": "same protocol with a single batch in flight (pipeline depth 1): the latency of "
+                                         "a step; the headline keeps `pipeline_depth` batches in flight on separate HIP "
+                                         "streams (eabnet_amd.Pipeline), results bit-identical"}
+    out["whole_path"]["one_step_at_a_time_frac"] = (out["gflop_per_step_algorithmic"] / out["one_step_at_a_time"]["ms_per_step"]
+                                                    / PEAK_FP32_MFMA_TFLOPS)
 
     # secondary measurement: the same timed protocol with the f16x3 contraction mode
     # (DESIGN.md §4.4).  The headline `value` stays on exact-fp32 arithmetic.
@@ -985,11 +1032,7 @@ def main():
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
     except Exception as e:  # noqa: BLE001
         out["secondary_sections_error"] = repr(e)
-    if rank == 0:
-        print(json.dumps(out))
-    if is_dist:
-        dist.barrier()
-        torch.distributed.destroy_process_group()
+    emit(out)
 
 
 if __name__ == "__main__":

@@ -52,3 +52,20 @@ def test_bench_accepts_the_drivers_flags_and_reads_the_rendezvous_from_the_envir
         assert re.search(r'add_argument\("%s"' % flag, src), flag
     for var in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         assert var in src or var in open(os.path.join(ROOT, "eabnet_amd", "dist.py")).read(), var
+
+
+def test_bench_offers_full_and_dump_outputs():
+    """A plain run times the headline only; `--full` carries the secondary sections and `--dump-outputs DIR` the last step's
+    output.  Checked through bench.py's own argument parser (it rejects its options before any device call)."""
+    import subprocess
+    import sys
+    bench = os.path.join(ROOT, "bench.py")
+    r = subprocess.run([sys.executable, bench, "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    for flag in ("--full", "--dump-outputs"):
+        assert flag in r.stdout, flag
+    # the per-op table is written by the instrumented replay, which only --full runs
+    r = subprocess.run([sys.executable, bench, "--per-op", os.devnull], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--full" in r.stderr, r.stderr
+    src = open(bench).read()
+    assert re.search(r'np\.save\(os\.path\.join\(a\.dump_outputs', src), "bench.py never writes the dumped output"
