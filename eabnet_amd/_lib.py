@@ -12,14 +12,15 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libeabnet_hip.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_TAPS = 16
 _fp = C.POINTER(C.c_float)
 
 
 class TimeWindow(C.Structure):
-    """mirror of eab_time_window: device pointer to the current frame position + frames per chunk"""
-    _fields_ = [("pos", C.c_void_p), ("count", C.c_int32)]
+    """mirror of eab_time_window: device pointer to the current frame position + frames per chunk, device pointer to
+    the per-utterance frame counts (or None)"""
+    _fields_ = [("pos", C.c_void_p), ("count", C.c_int32), ("lens", C.c_void_p)]
 
 
 class ConvDesc(C.Structure):

@@ -29,3 +29,12 @@ __device__ __forceinline__ float eab_tanh(float x) {
     return copysignf(t, x);
 }
 __device__ __forceinline__ float eab_prelu(float x, float a) { return x > 0.0f ? x : a * x; }
+
+// longest frame count (eab_time_window.lens) among the utterances of sequences [s0, s0 + n) of a [B][F] sequence set (S = B*F);
+// workgroup-uniform arguments, so the loads are scalar
+__device__ __forceinline__ int eab_max_len(const int* lens, int s0, int n, int S, int F) {
+    const int b_hi = ((s0 + n < S ? s0 + n : S) - 1) / F;
+    int m = 0;
+    for (int b = s0 / F; b <= b_hi; ++b) m = lens[b] > m ? lens[b] : m;
+    return m;
+}

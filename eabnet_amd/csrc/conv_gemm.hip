@@ -144,8 +144,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 
     // rows per batch element: all of them, or the streaming window [t_lo, t_lo + count) (eab_time_window)
     const int t_lo = d.win.pos ? *d.win.pos : 0;
-    const int t_hi = d.win.pos ? (t_lo + d.win.count < d.T ? t_lo + d.win.count : d.T) : d.T;
-    const int Q = t_hi * d.No;                      // first row NOT computed
+    int t_hi = d.win.pos ? (t_lo + d.win.count < d.T ? t_lo + d.win.count : d.T) : d.T;
     const int tiles_per_b = ((d.win.pos ? d.win.count : d.T) * d.No + BM - 1) / BM;
     // Workgroups are dealt to the 8 XCDs round-robin by blockIdx.x, and every XCD has its own L2: let each XCD walk one
     // contiguous eighth of the (b, tile) sequence, so that the k_t halo row two neighbouring tiles share (and the weights they
@@ -157,6 +156,10 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     }
     const int b = (int)(vblk / (unsigned)tiles_per_b);
     const int tile = (int)vblk - b * tiles_per_b;
+    // per-utterance length (eab_time_window.lens): rows of the padding frames are neither computed nor counted in the
+    // statistics partials (a tile wholly past the length writes an n = 0 partial and still arrives at fz_counter)
+    if (d.win.lens) t_hi = min(t_hi, d.win.lens[b]);
+    const int Q = t_hi * d.No;                      // first row NOT computed
     const int q0 = t_lo * d.No + tile * BM;
     const int n_blk = blockIdx.y * BN;
     const float inv_no = 1.0f / (float)d.No;
@@ -270,6 +273,9 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 
     __syncthreads();   // tap tables (and transform tables) visible
 
+    // A tile wholly past the rows to compute (streaming window past the utterance end, padding frames of a per-utterance
+    // length) skips the main loop: its accumulators stay zero, the epilogue stores nothing and the partial counts n = 0.
+    if (q0 < Q) {
     if constexpr (PATCH) {
         // ------------------------------------------------------------------------------
         // PATCH pipeline.  K is walked chunk-major (16 channels of ALL taps, then the next
@@ -835,6 +841,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     }
 
     }
+    }   // q0 < Q
 
     // ---- epilogue ---------------------------------------------------------------
     // C/D map of the 32x32 MFMA: column = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).

@@ -46,7 +46,8 @@
     const int ntaps = ph1 ? d.ph1_ntaps : d.ntaps;
     const int Kpad = ph1 ? d.ph1_Kpad : d.Kpad;
     const float* wfrag = ph1 ? d.ph1_w : d.w;
-    const int Q = t_hi * No;
+    // per-utterance length (eab_time_window.lens): padding frames are neither computed nor counted in the partials
+    const int Q = (d.win.lens ? min(t_hi, d.win.lens[b]) : t_hi) * No;
     const int q0 = t_lo * No + tile * BM;
     const float inv_no = 1.0f / (float)No;
     // row stride of the A tiles in ELEMENTS (fp32, or bf16 in the BF form): 16 bytes of padding per row

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void bfw_filter_sum_kernel(
     const float* __restrict__ y1, const float* __restrict__ w2, const float* __restrict__ b2,
     const float* __restrict__ x, float* __restrict__ out, float* __restrict__ bfw, int T, int F, int M,
     long long bins, const int* __restrict__ t_pos, int t_count, const float* __restrict__ w1,
-    const float* __restrict__ b1) {
+    const float* __restrict__ b1, const int* __restrict__ lens) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* ytile = smem;                            // [BFW_ROWS][BFW_K + 4]
     float* wl = smem + BFW_ROWS * (BFW_K + 4);      // [2M][BFW_K + 4]
@@ -258,6 +258,10 @@ __global__ __launch_bounds__(256) void bfw_filter_sum_kernel(
     accr += __shfl_xor(accr, 1); acci += __shfl_xor(acci, 1);
     accr += __shfl_xor(accr, 2); acci += __shfl_xor(acci, 2);
     if (valid && p == 0) {                           // out[b][ri][t][f], t * F + f = opos
+        if (lens && opos >= lens[ob] * F) {          // per-utterance length: the padding frames are zeros (by selection)
+            accr = 0.0f;
+            acci = 0.0f;
+        }
         out[(size_t)(ob * 2 + 0) * TF + opos] = accr;
         out[(size_t)(ob * 2 + 1) * TF + opos] = acci;
     }
@@ -289,9 +293,9 @@ extern "C" int eab_mlp_bfw_filter_sum_f32(const float* y1, const float* w1, cons
     size_t shmem = (size_t)(BFW_ROWS + 2 * M + (w1 ? BFW_K : 0)) * (BFW_K + 4) * sizeof(float);
     if (w1)
         hipLaunchKernelGGL(bfw_filter_sum_kernel<true>, dim3((unsigned)grid), dim3(256), shmem, eab_stream(stream), y1, w2,
-                           b2, x, out, bfw, T, F, M, bins, win.pos, win.count, w1, b1);
+                           b2, x, out, bfw, T, F, M, bins, win.pos, win.count, w1, b1, win.lens);
     else
         hipLaunchKernelGGL(bfw_filter_sum_kernel<false>, dim3((unsigned)grid), dim3(256), shmem, eab_stream(stream), y1, w2,
-                           b2, x, out, bfw, T, F, M, bins, win.pos, win.count, w1, b1);
+                           b2, x, out, bfw, T, F, M, bins, win.pos, win.count, w1, b1, win.lens);
     EAB_RETURN_LAUNCH_STATUS();
 }

@@ -16,13 +16,15 @@
 #define GAG_THREADS 256
 
 // Both kernels: one (b, t) row per workgroup; with a streaming window (eab_time_window) the grid covers
-// [B][count] rows starting at frame *t_pos and rows past the utterance end exit.
+// [B][count] rows starting at frame *t_pos and rows past the utterance end exit.  Per-utterance lengths (win.lens): the pack
+// skips the padding frames t >= lens[b], the CRM writes them as zeros (the stage output's defined padding).
 __global__ __launch_bounds__(GAG_THREADS) void gag_pack_kernel(const float* __restrict__ inpt, const float* __restrict__ pre_x,
                                                                float* __restrict__ enc_in, float* __restrict__ pre,
-                                                               int T, int F, int ld, const int* __restrict__ t_pos, int t_count) {
+                                                               int T, int F, int ld, const int* __restrict__ t_pos, int t_count,
+                                                               const int* __restrict__ lens) {
     const int Tw = t_pos ? t_count : T;
     const int b = blockIdx.x / Tw, t = (t_pos ? *t_pos : 0) + (blockIdx.x - b * Tw);
-    if (t >= T) return;
+    if (t >= T || (lens && t >= lens[b])) return;
     const int bt = b * T + t;
     const size_t plane = (size_t)T * F;
     const float* ir = inpt + ((size_t)b * 2) * plane + (size_t)t * F;
@@ -46,16 +48,21 @@ __global__ __launch_bounds__(GAG_THREADS) void gag_crm_kernel(const float* __res
                                                               const float* __restrict__ r, const float* __restrict__ i,
                                                               float* __restrict__ pre_out, float* __restrict__ planar,
                                                               int T, int F, int ld, int lin_ld, int act,
-                                                              const int* __restrict__ t_pos, int t_count) {
+                                                              const int* __restrict__ t_pos, int t_count,
+                                                              const int* __restrict__ lens) {
     const int Tw = t_pos ? t_count : T;
     const int b = blockIdx.x / Tw, t = (t_pos ? *t_pos : 0) + (blockIdx.x - b * Tw);
     if (t >= T) return;
+    const bool pad = lens && t >= lens[b];          // padding frame: zeros by selection (nothing of the frame is read)
     const int bt = b * T + t;
     const size_t plane = (size_t)T * F;
     float* o_r = planar + ((size_t)b * 2) * plane + (size_t)t * F;
     for (int f = threadIdx.x; f < ld / 2; f += GAG_THREADS) {
         float2 y = make_float2(0.0f, 0.0f);
-        if (f < F) {
+        if (f < F && pad) {
+            o_r[f] = 0.0f;
+            o_r[plane + f] = 0.0f;
+        } else if (f < F) {
             const float2 p = *reinterpret_cast<const float2*>(&pre[(size_t)bt * ld + 2 * f]);
             const float gain = gag_act(g[(size_t)bt * lin_ld + f], act);
             y = make_float2(p.x * gain + r[(size_t)bt * lin_ld + f], p.y * gain + i[(size_t)bt * lin_ld + f]);
@@ -72,7 +79,7 @@ extern "C" int eab_gag_pack_f32(const float* inpt, const float* pre_x, float* en
     EAB_CHECK_ARG(ld >= 2 * F && (ld % 4) == 0 && (long long)B * T < (1ll << 31));
     EAB_CHECK_ARG(win.pos == nullptr || win.count > 0);
     hipLaunchKernelGGL(gag_pack_kernel, dim3(B * (win.pos ? win.count : T)), dim3(GAG_THREADS), 0, eab_stream(stream), inpt,
-                       pre_x, enc_in, pre, T, F, ld, win.pos, win.count);
+                       pre_x, enc_in, pre, T, F, ld, win.pos, win.count, win.lens);
     EAB_RETURN_LAUNCH_STATUS();
 }
 
@@ -84,7 +91,7 @@ extern "C" int eab_gag_crm_f32(const float* pre, const float* g, const float* r,
     EAB_CHECK_ARG(act == EAB_ACT_SIGMOID || act == EAB_ACT_TANH || act == EAB_ACT_RELU);
     EAB_CHECK_ARG(win.pos == nullptr || win.count > 0);
     hipLaunchKernelGGL(gag_crm_kernel, dim3(B * (win.pos ? win.count : T)), dim3(GAG_THREADS), 0, eab_stream(stream), pre, g,
-                       r, i, pre_out, planar, T, F, ld, lin_ld, act, win.pos, win.count);
+                       r, i, pre_out, planar, T, F, ld, lin_ld, act, win.pos, win.count, win.lens);
     EAB_RETURN_LAUNCH_STATUS();
 }
 

@@ -58,7 +58,8 @@ __global__ __launch_bounds__(256) void lstm64_kernel(const float* __restrict__ x
                                                      const float* __restrict__ wcat, const float* __restrict__ bias,
                                                      float* __restrict__ h_out, int T, int F, int S,
                                                      const int* __restrict__ t_pos, int t_count,
-                                                     float* __restrict__ c_state, float* __restrict__ gates) {
+                                                     float* __restrict__ c_state, float* __restrict__ gates,
+                                                     const int* __restrict__ lens = nullptr) {
     __shared__ __attribute__((aligned(16))) float xs[2][LS_SEQ * LS_LD];
     __shared__ __attribute__((aligned(16))) float hs[2][LS_SEQ * LS_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -66,7 +67,10 @@ __global__ __launch_bounds__(256) void lstm64_kernel(const float* __restrict__ x
     const int s0 = blockIdx.x * LS_SEQ;
     // streaming (eab_time_window): steps [t_lo, t_hi) only; h_{t_lo-1} comes back from h_out, c from c_state
     const int t_lo = t_pos ? *t_pos : 0;
-    const int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
+    int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
+    // per-utterance lengths (eab_time_window.lens): the recurrence stops after the longest utterance among this workgroup's
+    // sequences (sequence s belongs to utterance s / F); later steps of the others are padding, never read
+    if (lens) t_hi = min(t_hi, eab_max_len(lens, s0, LS_SEQ, S, F));
 
     // ---- stationary weights: w?[g][4j+s] = Wcat[g*64 + 16w + ln][(x:0 | h:64) + 16j + 4*lk + s]
     float wx[4][16], wh[4][16];
@@ -284,7 +288,8 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
                                                        const float* __restrict__ wcat, const float* __restrict__ bias,
                                                        float* __restrict__ h_out, int T, int F, int S,
                                                        const int* __restrict__ t_pos, int t_count,
-                                                       float* __restrict__ c_state, float* __restrict__ gates = nullptr) {
+                                                       float* __restrict__ c_state, float* __restrict__ gates = nullptr,
+                                                       const int* __restrict__ lens = nullptr) {
     constexpr int NSEQ = 4 * G;
     constexpr int NCH = G == 1 ? 8 : (G == 2 ? 4 : 2);       // accumulation chains per group (>= 6 in flight overall)
     __shared__ __attribute__((aligned(16))) float xs[2][NSEQ * LS_LD];
@@ -293,7 +298,10 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
     const int gate = lane & 3, u = wave * 16 + (lane >> 2);
     const int s0 = blockIdx.x * NSEQ;
     const int t_lo = t_pos ? *t_pos : 0;
-    const int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
+    int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
+    // per-utterance lengths (eab_time_window.lens): the recurrence stops after the longest utterance among this workgroup's
+    // sequences (sequence s belongs to utterance s / F); later steps of the others are padding, never read
+    if (lens) t_hi = min(t_hi, eab_max_len(lens, s0, NSEQ, S, F));
 
     // stationary weights: this lane's gate column of [W_x | W_h]
     float wx[64], wh[64];
@@ -450,18 +458,18 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
 template <int G>
 static void lstm64_q_launch(bool ln, int grid, hipStream_t st, const float* x, const float* ln_g, const float* ln_b,
                             float ln_eps, const float* wcat, const float* bias, float* h_out, int T, int F, int S,
-                            const int* t_pos, int t_count, float* cs) {
+                            const int* t_pos, int t_count, float* cs, const int* lens) {
     if (ln)
         hipLaunchKernelGGL((lstm64_q_kernel<true, G>), dim3(grid), dim3(256), 0, st, x, ln_g, ln_b, ln_eps, wcat, bias,
-                           h_out, T, F, S, t_pos, t_count, cs);
+                           h_out, T, F, S, t_pos, t_count, cs, nullptr, lens);
     else
         hipLaunchKernelGGL((lstm64_q_kernel<false, G>), dim3(grid), dim3(256), 0, st, x, ln_g, ln_b, ln_eps, wcat, bias,
-                           h_out, T, F, S, t_pos, t_count, cs);
+                           h_out, T, F, S, t_pos, t_count, cs, nullptr, lens);
 }
 
 int eab_lstm64_h3_launch(const float* x, const float* ln_g, const float* ln_b, float ln_eps, const float* wcat,
                          const float* bias, float* h_out, int T, int F, int S, int precision, const int* t_pos, int t_count,
-                         float* c_state, hipStream_t stream);   // lstm_h3.hip
+                         float* c_state, const int* lens, hipStream_t stream);   // lstm_h3.hip
 
 extern "C" int eab_lstm64_f32(const float* x, const float* ln_g, const float* ln_b, float ln_eps, const float* wcat,
                               const float* bias, float* h_out, int B, int T, int F, eab_stream_t stream) {
@@ -487,21 +495,21 @@ extern "C" int eab_lstm64_stream_f32(const float* x, const float* ln_g, const fl
     float* cs = win.pos ? c_state : nullptr;
     if (precision != EAB_PREC_F32)      // streaming state (h in h_out, c in c_state) is carried in fp32 in every mode
         return eab_lstm64_h3_launch(x, ln_g, ln_b, ln_eps, wcat, bias, h_out, T, F, (int)S, precision, win.pos, win.count, cs,
-                                    eab_stream(stream));
+                                    win.lens, eab_stream(stream));
     // up to 2048 sequences (12 four-second utterances): 4-sequence workgroups on the 4x4x1 MFMA (measured faster
     // than the 16-sequence kernel up to there, even at two workgroups per CU; larger groups never won)
     if (S <= 2048) {
         lstm64_q_launch<1>(ln_g != nullptr, (int)((S + 3) / 4), eab_stream(stream), x, ln_g, ln_b, ln_eps, wcat, bias, h_out,
-                           T, F, (int)S, win.pos, win.count, cs);
+                           T, F, (int)S, win.pos, win.count, cs, win.lens);
         EAB_RETURN_LAUNCH_STATUS();
     }
     const int grid = (int)((S + LS_SEQ - 1) / LS_SEQ);
     if (ln_g)
         hipLaunchKernelGGL((lstm64_kernel<true, false>), dim3(grid), dim3(256), 0, eab_stream(stream), x, ln_g, ln_b, ln_eps,
-                           wcat, bias, h_out, T, F, (int)S, win.pos, win.count, cs, nullptr);
+                           wcat, bias, h_out, T, F, (int)S, win.pos, win.count, cs, nullptr, win.lens);
     else
         hipLaunchKernelGGL((lstm64_kernel<false, false>), dim3(grid), dim3(256), 0, eab_stream(stream), x, ln_g, ln_b, ln_eps,
-                           wcat, bias, h_out, T, F, (int)S, win.pos, win.count, cs, nullptr);
+                           wcat, bias, h_out, T, F, (int)S, win.pos, win.count, cs, nullptr, win.lens);
     EAB_RETURN_LAUNCH_STATUS();
 }
 

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
                                                         const float* __restrict__ wcat, const float* __restrict__ bias,
                                                         float* __restrict__ h_out, int T, int F, int S,
                                                         const int* __restrict__ t_pos, int t_count, float* __restrict__ c_state,
-                                                        float* __restrict__ gates = nullptr) {
+                                                        float* __restrict__ gates = nullptr, const int* __restrict__ lens = nullptr) {
     using v8 = std::conditional_t<BF, bf16x8, h16x8>;
     using e16 = std::conditional_t<BF, __bf16, _Float16>;
     __shared__ __attribute__((aligned(16))) char xs[2][LH_SEQ * LH_ROW];
@@ -87,7 +87,10 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
     const int s0 = blockIdx.x * NS;
     // streaming (eab_time_window): steps [t_lo, t_hi) only
     const int t_lo = t_pos ? *t_pos : 0;
-    const int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
+    int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
+    // per-utterance lengths (eab_time_window.lens): the recurrence stops after the longest utterance among this workgroup's
+    // sequences (sequence s belongs to utterance s / F); later steps of the others are padding, never read
+    if (lens) t_hi = min(t_hi, eab_max_len(lens, s0, NS, S, F));
 
     // ---- stationary weights as 16-bit hi/lo B fragments (bf16 mode: hi only is multiplied):
     //      w?[g][kb] = W[g*64 + 16w + ln][(x:0 | h:64) + 32*kb + 8*lk + j], j = 0..7
@@ -317,11 +320,11 @@ int eab_lstm64_bf_train_launch(const float* x, const float* wcat, const float* b
 // dispatcher shared with csrc/lstm.hip
 int eab_lstm64_h3_launch(const float* x, const float* ln_g, const float* ln_b, float ln_eps, const float* wcat,
                          const float* bias, float* h_out, int T, int F, int S, int precision, const int* t_pos, int t_count,
-                         float* c_state, hipStream_t stream) {
+                         float* c_state, const int* lens, hipStream_t stream) {
     const int grid = (S + LH_SEQ - 1) / LH_SEQ;
 #define LH_GO(LN_, BF_)                                                                                                     \
     hipLaunchKernelGGL((lstm64_h3_kernel<LN_, BF_>), dim3(grid), dim3(256), 0, stream, x, ln_g, ln_b, ln_eps, wcat, bias, h_out, \
-                       T, F, S, t_pos, t_count, c_state)
+                       T, F, S, t_pos, t_count, c_state, nullptr, lens)
     if (precision == EAB_PREC_BF16) {
         if (ln_g) LH_GO(true, true); else LH_GO(false, true);
     } else {

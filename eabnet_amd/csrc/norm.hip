@@ -98,14 +98,17 @@ __global__ __launch_bounds__(256) void norm_act_kernel(const float* __restrict__
                                                        const float* __restrict__ sla, const float* __restrict__ bb,
                                                        const float* __restrict__ xfb, const float* __restrict__ slb,
                                                        float* __restrict__ out, int P, int C,
-                                                       const int* __restrict__ t_pos, int rows_per_t, int Pw) {
+                                                       const int* __restrict__ t_pos, int rows_per_t, int Pw,
+                                                       const int* __restrict__ lens) {
     // rows computed per batch element: all P, or the Pw rows of the streaming window starting at row
-    // *t_pos * rows_per_t (clipped at P: the last chunk may be shorter than the window)
+    // *t_pos * rows_per_t (clipped at P: the last chunk may be shorter than the window), or -- per-utterance lengths
+    // (eab_time_window.lens) -- the rows of the first lens[b] frames
     const unsigned C4 = (unsigned)C >> 2;
-    const unsigned p_lo = t_pos ? (unsigned)*t_pos * (unsigned)rows_per_t : 0u;
-    const unsigned rows = t_pos ? ((unsigned)Pw < (unsigned)P - p_lo ? (unsigned)Pw : (unsigned)P - p_lo) : (unsigned)P;
-    const unsigned n4 = p_lo < (unsigned)P ? rows * C4 : 0u;
     const unsigned b = blockIdx.y;
+    const unsigned p_lo = t_pos ? (unsigned)*t_pos * (unsigned)rows_per_t : 0u;
+    unsigned rows = t_pos ? ((unsigned)Pw < (unsigned)P - p_lo ? (unsigned)Pw : (unsigned)P - p_lo) : (unsigned)P;
+    if (lens && !t_pos) rows = min(rows, (unsigned)lens[b] * (unsigned)rows_per_t);
+    const unsigned n4 = p_lo < (unsigned)P ? rows * C4 : 0u;
     const size_t base = ((size_t)b * P + p_lo) * C4;
     const unsigned stride = gridDim.x * blockDim.x, start = blockIdx.x * blockDim.x + threadIdx.x;
     f32x4 s01, s23, sl, t01, t23, tl;
@@ -169,7 +172,7 @@ extern "C" int eab_norm_act_win_f32(const float* a, const float* xfa, const floa
     hipStream_t s = eab_stream(stream);
     const bool hoist = 256 % (C / 4) == 0;
 #define NA_LAUNCH(H_, T_) hipLaunchKernelGGL((norm_act_kernel<H_, T_>), grid, block, 0, s, a, xfa, slopea, b, xfb, slopeb, out, (int)P, C, \
-                                              win.pos, rows_per_t, (int)Pw)
+                                              win.pos, rows_per_t, (int)Pw, win.lens)
     if (hoist) {
         if (b) NA_LAUNCH(true, true); else NA_LAUNCH(true, false);
     } else {

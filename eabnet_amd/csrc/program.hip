@@ -71,7 +71,7 @@ extern "C" int eab_run_program(const eab_op* ops, int n_ops, eab_stream_t stream
                                             (float*)o.p[8], stream);
                 break;
             case EAB_OP_NORM_ACT:
-                if (o.win.pos)
+                if (o.win.pos || o.win.lens)
                     rc = o.i[3] > 0 && o.i[1] % o.i[3] == 0
                              ? eab_norm_act_win_f32((const float*)o.p[0], (const float*)o.p[1], (const float*)o.p[2],
                                                     (const float*)o.p[3], (const float*)o.p[4], (const float*)o.p[5],

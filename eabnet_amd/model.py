@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+from collections import OrderedDict
 from typing import Dict, Optional, Tuple
 
 import numpy as np
@@ -87,6 +88,9 @@ class _Bound:
         # streaming programs: the frame position every windowed op reads (device memory, so one captured
         # graph serves all chunks)
         self.t_pos = torch.zeros(1, dtype=torch.int32, device=device) if prog.chunk else None
+        # per-utterance lengths (varlen programs): device array [B] every windowed op reads; written on the launch stream
+        # before each run, so one captured graph serves every combination of lengths
+        self.lens = torch.full((prog.B,), prog.T, dtype=torch.int32, device=device) if prog.varlen else None
         self._in_ptr = None
         self._out_ptr = None
         # hipGraph replay (optional): static boundary buffers + the captured program
@@ -165,6 +169,8 @@ class _Bound:
             if getattr(op, "win", False):
                 w = o.conv.win if op.kind == prg.OP_CONV else o.win
                 w.pos, w.count = self.t_pos.data_ptr(), self.prog.chunk
+            if self.lens is not None and hasattr(op, "win"):
+                (o.conv.win if op.kind == prg.OP_CONV else o.win).lens = self.lens.data_ptr()
             if op.kind == prg.OP_CONV:
                 d = o.conv
                 for f in ("src0", "src1", "xf0", "xf1", "slope0", "slope1", "w", "bias", "aux", "dst", "dst_acc",
@@ -371,6 +377,39 @@ def graph_branches_allowed() -> bool:
     return os.environ.get("EAB_GRAPH_BRANCHES", "1") != "0"
 
 
+AUTO_BUCKETS = tuple(64 << k for k in range(8))          # length_buckets="auto": 64, 128, .., 8192 frames
+
+
+def bucket_for(T: int, caps) -> Optional[int]:
+    """smallest cap >= T, or None when T exceeds every cap (the call then takes the exact-shape path)"""
+    for c in caps:
+        if c >= T:
+            return int(c)
+    return None
+
+
+def check_lengths(lengths, B: int, T: int):
+    """Validate a ``lengths=`` argument: a (B,) sequence or integer tensor with 1 <= len <= T.  Host values are checked and
+    returned as a list; a device tensor is checked for shape and dtype only (its values would need a host synchronisation)
+    and returned as is -- the kernels stay in bounds for any value."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dtype.is_floating_point or lengths.dtype == torch.bool or lengths.is_complex():
+            raise ValueError(f"lengths must be integers, got {lengths.dtype}")
+        if tuple(lengths.shape) != (B,):
+            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+        if lengths.is_cuda:
+            return lengths
+        vals = [int(v) for v in lengths.tolist()]
+    else:
+        vals = [int(v) for v in lengths]
+        if len(vals) != B:
+            raise ValueError(f"lengths must hold {B} values (one per utterance), got {len(vals)}")
+    bad = [v for v in vals if not 1 <= v <= T]
+    if bad:
+        raise ValueError(f"lengths must lie in [1, {T}] (the call's frame count), got {bad[:4]}")
+    return vals
+
+
 def _refuse_differentiable(module: nn.Module, what: str, reason: str):
     """A differentiable call the HIP training programs do not cover is refused, never served by another backend: the package
     has one (the PyTorch-ROCm operator evaluation that used to sit here is now test infrastructure, tests/operator_path.py)."""
@@ -401,6 +440,16 @@ class _HipModule(nn.Module):
         self.precision = "f32"
         # "hip" once a differentiable forward has run (train.py / train_gag.py programs -- the only backend); None before
         self.training_backend = None
+        # length-bucketed programs (causal configurations, inference): None = one exact-shape program per (B, T), as always;
+        # "auto" = caps of 64, 128, .. 8192 frames; or an ascending tuple of caps.  A call of T frames then runs in the
+        # program of the smallest cap >= T with every utterance T frames long (lengths = T) and is sliced back to T; longer
+        # calls take the exact-shape path.  Bucketed programs live in an LRU of their own, bounded by a count and by the
+        # bytes of their activation arenas (varlen_arena_bytes() reports them per bucket).
+        self.length_buckets = None
+        self.max_resident_programs = 8
+        self.max_resident_bytes = 8 << 30
+        self._varlen_bound: "OrderedDict[tuple, _Bound]" = OrderedDict()
+        self._varlen_version: Dict[tuple, tuple] = {}
 
     def _param_fingerprint(self) -> tuple:
         """Change detector for the packed weights (runs on every forward).  Every parameter / buffer slot
@@ -442,6 +491,106 @@ class _HipModule(nn.Module):
             bound.update_weights(prog.weights)
             self._packed_version[key] = fp
         return bound
+
+    # -- per-utterance lengths / length buckets ----------------------------------------
+    def _bucket_caps(self) -> Tuple[int, ...]:
+        lb = self.length_buckets
+        if lb is None:
+            return ()
+        if isinstance(lb, str):
+            if lb != "auto":
+                raise ValueError(f"length_buckets must be None, 'auto' or an ascending tuple of frame counts, got {lb!r}")
+            return AUTO_BUCKETS
+        caps = tuple(int(c) for c in lb)
+        if not caps or any(c < 1 for c in caps) or any(b <= a for a, b in zip(caps, caps[1:])):
+            raise ValueError(f"length_buckets must be an ascending tuple of positive frame counts, got {lb!r}")
+        return caps
+
+    def _varlen_call(self, T: int, B: int, lengths, needs_graph: bool) -> Optional[Tuple[int, object]]:
+        """(T_cap, lengths) of a call that runs in a per-utterance-length program, or None for the exact-shape path.
+        Explicit ``lengths`` are validated here (ValueError) and refused (NotImplementedError) where they cannot be served."""
+        if lengths is None:
+            if self.length_buckets is None or not self.cfg.is_causal or needs_graph or self.dump_bfw:
+                return None
+            cap = bucket_for(T, self._bucket_caps())
+            return None if cap is None else (cap, T)
+        lens = check_lengths(lengths, B, T)
+        if needs_graph:
+            raise _refuse_differentiable(self, "lengths= under autograd (or BatchNorm in train mode)",
+                                         "per-utterance lengths are an inference form; training with lengths (masked batch "
+                                         "statistics, gradients) is not implemented")
+        if not self.cfg.is_causal:
+            raise NotImplementedError(f"{type(self).__name__}: lengths= needs is_causal=True -- the non-causal S-TCM taps of "
+                                      "the last frames of an utterance read the frames after it, so a padded batch cannot "
+                                      "reproduce the one-at-a-time result")
+        if self.dump_bfw:
+            raise NotImplementedError(f"{type(self).__name__}: lengths= with dump_bfw (a test hook of the exact-shape path)")
+        cap = bucket_for(T, self._bucket_caps()) if self.length_buckets is not None else None
+        return (cap if cap is not None else T), lens
+
+    def _varlen_program(self, B: int, T_cap: int, F: int, device: torch.device) -> _Bound:
+        chains = bool(self.__dict__.get("parallel_chains", True))
+        key = (B, T_cap, F, str(device), self.precision, chains)
+        fp = self._param_fingerprint()
+        bound = self._varlen_bound.get(key)
+        if bound is None:
+            prog = prg.lower(self.cfg, self._numpy_params(), B, T_cap, F, precision=self.precision,
+                             parallel_chains=chains, varlen=True)
+            need = 4 * max(prog.act_floats, 1)
+            while self._varlen_bound and (len(self._varlen_bound) >= self.max_resident_programs or
+                                          sum(4 * b.acts.numel() for b in self._varlen_bound.values()) + need
+                                          > self.max_resident_bytes):
+                old, _ = self._varlen_bound.popitem(last=False)            # least recently used
+                self._varlen_version.pop(old, None)
+            bound = _Bound(prog, device)
+            self._varlen_bound[key] = bound
+            self._varlen_version[key] = fp
+        elif self._varlen_version.get(key) != fp:
+            prog = prg.lower(self.cfg, self._numpy_params(), B, T_cap, F, precision=self.precision,
+                             parallel_chains=chains, varlen=True)
+            bound.update_weights(prog.weights)
+            self._varlen_version[key] = fp
+        self._varlen_bound.move_to_end(key)
+        return bound
+
+    def varlen_arena_bytes(self) -> Dict[tuple, int]:
+        """Activation-arena bytes of every resident length-bucketed program, keyed (B, T_cap, F, device, precision, chains)."""
+        return {k: 4 * b.acts.numel() for k, b in self._varlen_bound.items()}
+
+    def _run_varlen(self, T_cap: int, lens, inputs, out_shape) -> Tuple[_Bound, torch.Tensor]:
+        """Run the per-utterance-length program of cap T_cap on ``inputs`` (time axis 1 for EaBNet's (B,T,F,M,2), 2 for
+        GaGNet's (B,2,T,F)); returns the full (.., T_cap, ..) output buffer.  The lengths reach the device array on the
+        launch stream (pinned host copy or device-to-device), with no host synchronisation."""
+        x0 = inputs[0]
+        tax = 1 if x0.ndim == 5 else 2
+        B, T = x0.shape[0], x0.shape[tax]
+        F = x0.shape[-1] if tax == 2 else x0.shape[2]
+        bound = self._varlen_program(B, T_cap, F, x0.device)
+        if isinstance(lens, int):
+            bound.lens.fill_(lens)
+        elif isinstance(lens, torch.Tensor) and lens.is_cuda:
+            bound.lens.copy_(lens.to(torch.int32), non_blocking=True)
+        else:
+            bound.lens.copy_(torch.as_tensor(lens, dtype=torch.int32).pin_memory(), non_blocking=True)
+        pad = lambda t: tuple(t.shape[:tax]) + (T_cap,) + tuple(t.shape[tax + 1:])  # noqa: E731
+        cap_out = tuple(out_shape[:-2]) + (T_cap, out_shape[-1])
+        in2 = pad(inputs[1]) if len(inputs) > 1 else None
+        if self.use_graph and not torch.cuda.is_current_stream_capturing() and bound.capture(pad(x0), cap_out, in2):
+            stat = [bound.static_in] + ([bound.static_in2] if in2 else [])
+            for dst, src in zip(stat, inputs):
+                dst.narrow(tax, 0, T).copy_(src, non_blocking=True)
+            bound.graph.replay()
+            return bound, bound.static_out
+        stat = []
+        for src in inputs:
+            buf = torch.zeros(pad(src), dtype=torch.float32, device=src.device)
+            buf.narrow(tax, 0, T).copy_(src)
+            stat.append(buf)
+        out = torch.empty(cap_out, dtype=torch.float32, device=x0.device)
+        bound.bind(stat[0].data_ptr(), out.data_ptr(), stat[1].data_ptr() if len(stat) > 1 else None)
+        bound.run(torch.cuda.current_stream().cuda_stream)
+        self._last_varlen = stat
+        return bound, out
 
     # -- streaming ------------------------------------------------------------------
     def stream_begin(self, B: int, T_max: int, chunk: int = 1, F: int = 161, device=None) -> EaBNetStream:
@@ -497,13 +646,29 @@ class EaBNet(_HipModule):
         self._init_params(param_specs(self.cfg))     # raises NotImplementedError for unsupported topologies
 
     # -- forward -------------------------------------------------------------------
-    def forward(self, inpt: torch.Tensor) -> torch.Tensor:
+    def forward(self, inpt: torch.Tensor, lengths=None) -> torch.Tensor:
         """:param inpt: (B, T, F, M, 2) compressed multichannel spectrogram
+        :param lengths: optional (B,) frame counts, 1 <= len <= T (causal configurations, inference): utterance b is
+            inpt[b, :len[b]]; frames >= len[b] of the input are ignored and those of the output are zero
         :return: beamformed estimate (B, 2, T, F)   (reference EaBNet.py:88-117)"""
         if inpt.ndim == 4:
             inpt = inpt.unsqueeze(-2)
         if inpt.ndim != 5 or inpt.shape[-1] != 2 or inpt.shape[-2] != self.M:
             raise ValueError(f"expected (B,T,F,{self.M},2), got {tuple(inpt.shape)}")
+        vl = self._varlen_call(inpt.shape[1], inpt.shape[0], lengths, self._needs_graph(inpt))
+        if vl is not None:
+            if not inpt.is_cuda:
+                raise _lib.EabError("eabnet_amd.EaBNet inference runs on MI355X only: move the input (and module) to 'cuda'.")
+            _lib.load()
+            B, T, F, M, _ = inpt.shape
+            x = inpt.detach().to(torch.float32)
+            with torch.cuda.device(x.device):
+                bound, full = self._run_varlen(vl[0], vl[1], (x,), (B, 2, T, F))
+                out = full[:, :, :T].clone()
+            self._last = (bound, x)
+            if self.topo_type == "miso":
+                out = out.sum(dim=-1)
+            return out.to(inpt.dtype)
         if self._needs_graph(inpt):
             # training: forward AND backward on the hand-written kernels (train.py: two static op programs behind one
             # autograd node) for every constructor branch; BatchNorm = train mode (batch statistics + buffer update)
@@ -627,6 +792,8 @@ def _replica(module: nn.Module) -> nn.Module:
     rep._modules = {k: (_replica(v) if v is not None else None) for k, v in module._modules.items()}
     if isinstance(rep, _HipModule):
         rep._bound, rep._packed_version = {}, {}
+        # the Pipeline serves exact shapes (its replicas own their programs; length buckets stay with the original module)
+        rep.length_buckets, rep._varlen_bound, rep._varlen_version = None, OrderedDict(), {}
         rep.__dict__.pop("_slot_list", None)
     return rep
 
@@ -837,11 +1004,27 @@ class GaGNet(_HipModule):
                              norm_type=norm_type)
         self._init_params(gag_param_specs(self.cfg))
 
-    def forward(self, inpt: torch.Tensor, pre_x: torch.Tensor) -> list:
+    def forward(self, inpt: torch.Tensor, pre_x: torch.Tensor, lengths=None) -> list:
         """:param inpt, pre_x: (B, 2, T, F) noisy reference-microphone spectrum and previous estimate
+        :param lengths: optional (B,) frame counts, 1 <= len <= T (causal configurations, inference); frames >= len[b] of
+            the inputs are ignored and those of every estimate are zero
         :return: list of q estimates (B, 2, F, T)   (reference GaGNet.py:76-90)"""
         if inpt.ndim != 4 or inpt.shape[1] != 2 or inpt.shape[3] != self.cfg.freq or pre_x.shape != inpt.shape:
             raise ValueError(f"expected two (B,2,T,{self.cfg.freq}) tensors, got {tuple(inpt.shape)} and {tuple(pre_x.shape)}")
+        vl = self._varlen_call(inpt.shape[2], inpt.shape[0], lengths, self._needs_graph(inpt, pre_x))
+        if vl is not None:
+            if not (inpt.is_cuda and pre_x.is_cuda):
+                raise _lib.EabError("eabnet_amd.GaGNet inference runs on MI355X only: move the inputs (and module) to 'cuda'.")
+            _lib.load()
+            B, _, T, F = inpt.shape
+            a = inpt.detach().to(torch.float32)
+            b = pre_x.detach().to(torch.float32)
+            with torch.cuda.device(a.device):
+                bound, full = self._run_varlen(vl[0], vl[1], (a, b), (self.q, B, 2, T, F))
+                out = full[:, :, :, :T].clone()
+            self._last = (bound, a, b)
+            out = out.to(inpt.dtype)
+            return [out[j].permute(0, 1, 3, 2) for j in range(self.q)]
         if self._needs_graph(inpt, pre_x):
             # training: forward AND backward on the hand-written kernels (train_gag.py).  No gradient flows to the inputs:
             # the reference feeds the detached beam-former estimate (EaBNet.py:142)
@@ -908,10 +1091,23 @@ class EaBNetWithPostNet(nn.Module):
         if args.freeze_eabnet:
             self.freeze_eabnet()
 
-    def forward(self, noisy_stft: torch.Tensor) -> dict:
-        esti0_stft = self.eabnet(noisy_stft)
+    @property
+    def length_buckets(self):
+        """length buckets of both stages (see EaBNet.length_buckets)"""
+        return self.eabnet.length_buckets
+
+    @length_buckets.setter
+    def length_buckets(self, value) -> None:
+        self.eabnet.length_buckets = value
+        self.postnet.length_buckets = value
+
+    def forward(self, noisy_stft: torch.Tensor, lengths=None) -> dict:
+        """lengths: optional (B,) frame counts, passed to both stages (EaBNet.forward)"""
+        if lengths is not None and isinstance(lengths, torch.Tensor) and not lengths.is_cuda:
+            lengths = lengths.tolist()                                          # validated once per stage, host values
+        esti0_stft = self.eabnet(noisy_stft, lengths=lengths)
         inpt = noisy_stft[..., self.ref_mic, :].permute(0, 3, 1, 2)            # 'b t f c -> b c t f'
-        esti1_stft_list = self.postnet(inpt, esti0_stft.detach())
+        esti1_stft_list = self.postnet(inpt, esti0_stft.detach(), lengths=lengths)
         return {"esti0_stft": esti0_stft, "esti1_stft_list": esti1_stft_list,
                 "esti_stft": esti1_stft_list[-1].permute(0, 1, 3, 2)}
 

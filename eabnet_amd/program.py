@@ -460,6 +460,9 @@ class Program:
     sync: Dict[int, list] = field(default_factory=dict)
     chunk: int = 0                 # > 0: streaming program, every op works on `chunk` frames from a device-side position
     zero_init: List[Tuple[Ref, int]] = field(default_factory=list)      # (arena ref, floats) that must be zero before the first replay
+    # > 0 / True: per-utterance lengths (eab_time_window.lens): utterance b is its first lens[b] frames, read by every windowed
+    # op from one device array [B] the binding owns (lower(..., varlen=True); causal configurations only)
+    varlen: bool = False
 
 
 class Lowering:
@@ -1308,13 +1311,26 @@ class GagLowering(Lowering):
 
 
 def lower(cfg, params: Dict[str, np.ndarray], B: int, T: int, F: int = 161,
-          dump_bfw: bool = False, precision: str = "f32", chunk: int = 0, parallel_chains: bool = True) -> Program:
+          dump_bfw: bool = False, precision: str = "f32", chunk: int = 0, parallel_chains: bool = True,
+          varlen: bool = False) -> Program:
     """chunk > 0 lowers the streaming form: T is then the longest utterance the resident activations can
     hold and every op advances `chunk` frames per replay.  parallel_chains (GaGNet): the glance / gaze S-TCM
     chains of a stage as parallel graph branches (best latency of one batch) or back to back (best when
-    several batches are in flight anyway, eabnet_amd.Pipeline)."""
+    several batches are in flight anyway, eabnet_amd.Pipeline).  varlen: a program for up to T frames per
+    utterance whose ops read per-utterance lengths from device memory (eab_time_window.lens): frames past an
+    utterance's length are skipped, left out of the InstanceNorm statistics and output as zeros.  Needs
+    is_causal=True (then every time dependence looks only at earlier frames, InstanceNorm statistics aside)."""
+    if varlen:
+        if not cfg.is_causal:
+            raise NotImplementedError("per-utterance lengths need is_causal=True: the non-causal S-TCM taps of frames "
+                                      "near the end of an utterance read the frames after it")
+        if chunk:
+            raise NotImplementedError("per-utterance lengths are an offline form; streaming carries its own position")
     if isinstance(cfg, GagConfig):
         low = GagLowering(cfg, params, B, T, F, False, precision, chunk)
         low.parallel_chains = parallel_chains
-        return low.build()
-    return Lowering(cfg, params, B, T, F, dump_bfw, precision, chunk).build()
+        prog = low.build()
+    else:
+        prog = Lowering(cfg, params, B, T, F, dump_bfw, precision, chunk).build()
+    prog.varlen = bool(varlen)
+    return prog

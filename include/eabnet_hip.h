@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define EAB_ABI_VERSION 8
+#define EAB_ABI_VERSION 9
 
 #define EAB_OK          0
 #define EAB_EINVAL      1   /* bad argument (shape, alignment, limit) */
@@ -47,10 +47,18 @@ const char* eab_error_string(int code);
  *     t in [*pos, min(*pos + count, T))
  * of its output and leaves every other row as it is -- older rows are the "state" later chunks read.
  * `pos` points to DEVICE memory, so ONE captured hipGraph is replayed for successive chunks after a
- * 4-byte update of the position; the launch geometry depends on `count` only. */
+ * 4-byte update of the position; the launch geometry depends on `count` only.
+ *
+ * Per-utterance lengths (offline programs of causal configurations, any norm): when `lens` is non-NULL it points to
+ * DEVICE memory holding B frame counts, 1 <= lens[b] <= T, and utterance b is taken to be its first lens[b] frames.
+ * Frames t >= lens[b] of the input are padding: no statistic (InstanceNorm partials) includes them, the convolutions and
+ * the LSTM recurrence skip them, and the network outputs (filter-and-sum, GaGNet's stage outputs) are written as exact
+ * zeros there; intermediate activations are left undefined past the length.  Frames below the length are computed
+ * exactly as by a program of T = lens[b] frames (causal taps read no later frame).  lens == NULL: the whole utterance. */
 typedef struct eab_time_window {
     const int32_t* pos;
     int32_t count;
+    const int32_t* lens;
 } eab_time_window;
 
 /* --------------------------------------------------------------------------
