@@ -22,7 +22,8 @@ import torch.nn as nn
 
 from . import _lib
 from . import program as prg
-from .graphs import LaneGraphs, plan_segments, single_lane
+from .graphs import LaneGraphs
+from .runtime import BoundProgram, graph_branches_allowed  # noqa: F401 (graph_branches_allowed: API)
 from .spec import GagConfig, NetConfig, ParamSpec, gag_param_specs, param_specs
 
 
@@ -75,30 +76,26 @@ def _attach(root: nn.Module, dotted: str, p: torch.Tensor) -> None:
 # ----------------------------------------------------------------------------
 # bound program
 # ----------------------------------------------------------------------------
-class _Bound:
-    """A lowered program with device arenas and the ctypes op array."""
+class _Bound(BoundProgram):
+    """A lowered inference program with its device arenas: the op list "run", bound to in / out (/ in2) buffers."""
+    BOUNDARY = ("in", "out", "in2")
 
     def __init__(self, prog: prg.Program, device: torch.device):
         self.prog = prog
-        self.device = device
         self.weights = torch.from_numpy(prog.weights).to(device)
         self.acts = torch.empty(max(prog.act_floats, 1), dtype=torch.float32, device=device)
+        super().__init__(device, {"w": self.weights, "a": self.acts}, {"run": prog.ops}, {"run": prog.lanes}, {"run": prog.sync})
+        self.ops = self.arrays["run"]
         self.reset_counters()
-        self.ops = (_lib.Op * len(prog.ops))()
         # streaming programs: the frame position every windowed op reads (device memory, so one captured
         # graph serves all chunks)
         self.t_pos = torch.zeros(1, dtype=torch.int32, device=device) if prog.chunk else None
         # per-utterance lengths (varlen programs): device array [B] every windowed op reads; written on the launch stream
         # before each run, so one captured graph serves every combination of lengths
         self.lens = torch.full((prog.B,), prog.T, dtype=torch.int32, device=device) if prog.varlen else None
-        self._in_ptr = None
-        self._out_ptr = None
-        # hipGraph replay (optional): static boundary buffers + the captured program
-        self.graph = None
-        self.static_in = None
-        self.static_in2 = None
-        self.static_out = None
-        self.graph_failed = False
+        self.window = {"t_pos": self.t_pos.data_ptr() if prog.chunk else None, "chunk": prog.chunk,
+                       "lens": self.lens.data_ptr() if prog.varlen else None}
+        self.exec_ops, self.n_exec, self.chains = None, 0, []
 
     def reset_counters(self) -> None:
         """arrival counters of the fused InstanceNorm finalisation: zero before the first run (the kernels re-arm them
@@ -116,137 +113,35 @@ class _Bound:
         except Exception:                                 # noqa: BLE001 - interpreter shutdown
             pass
 
-    def capture(self, in_shape, out_shape, in2_shape=None) -> bool:
-        """Capture the whole op program into a hipGraph bound to static in/out buffers.  Replaying it
-        costs one graph launch instead of ~250 kernel launches enqueued by the host.  Returns False
-        (and stays on direct launches) if the runtime refuses the capture."""
-        if self.graph is not None or self.graph_failed:
-            return self.graph is not None
-        try:
-            self.static_in = torch.empty(in_shape, dtype=torch.float32, device=self.device)
-            self.static_out = torch.empty(out_shape, dtype=torch.float32, device=self.device)
-            if in2_shape is not None:
-                self.static_in2 = torch.empty(in2_shape, dtype=torch.float32, device=self.device)
-            self.bind(self.static_in.data_ptr(), self.static_out.data_ptr(),
-                      self.static_in2.data_ptr() if in2_shape is not None else None)
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                 # warm-up outside the capture
-                self.static_in.zero_()
-                if self.static_in2 is not None:
-                    self.static_in2.zero_()
-                self._launch(side.cuda_stream, 0, len(self.prog.ops))      # (program order on one stream: no lanes to set up)
-            torch.cuda.current_stream().wait_stream(side)
-            # one single-stream hipGraph per lane segment (graphs.py: a hipGraph with internal branches can crash the HIP
-            # runtime at replay, depending on streams created elsewhere in the process); programs without parallel
-            # branches are one segment, i.e. one graph
-            lg = LaneGraphs(self.device, self._plan(), self._launch)
-            lg.capture()
-            self.graph = lg
-        except Exception as e:                            # noqa: BLE001 - any capture failure -> direct launches
-            import warnings
-            warnings.warn(f"eabnet_amd: hipGraph capture failed ({e!r}); using direct launches")
-            self.graph, self.graph_failed = None, True
-            self._in_ptr = None
-        return self.graph is not None
+    @property
+    def graph(self) -> Optional[LaneGraphs]:
+        """the captured program (None before a capture or after a refused one)"""
+        return self.graphs["run"] if self.graphs else None
+
+    # the captured form's boundary buffers (None before a capture)
+    static_in = property(lambda self: self.static.get("in"))
+    static_out = property(lambda self: self.static.get("out"))
+    static_in2 = property(lambda self: self.static.get("in2"))
 
     def update_weights(self, flat: np.ndarray) -> None:
         self.weights.copy_(torch.from_numpy(flat), non_blocking=False)
 
-    def _addr(self, ref: Optional[prg.Ref], bases) -> Optional[int]:
-        if ref is None:
-            return None
-        return bases[ref.arena] + 4 * ref.off
-
-    def bind(self, in_ptr: int, out_ptr: int, in2_ptr: Optional[int] = None) -> None:
-        if (in_ptr, out_ptr, in2_ptr) == self._in_ptr:
-            return
-        bases = {"w": self.weights.data_ptr(), "a": self.acts.data_ptr(), "in": in_ptr, "out": out_ptr, "in2": in2_ptr}
-        A = lambda r: self._addr(r, bases)  # noqa: E731
-        for k, op in enumerate(self.prog.ops):
-            o = self.ops[k]
-            o.kind = op.kind
-            if getattr(op, "win", False):
-                w = o.conv.win if op.kind == prg.OP_CONV else o.win
-                w.pos, w.count = self.t_pos.data_ptr(), self.prog.chunk
-            if self.lens is not None and hasattr(op, "win"):
-                (o.conv.win if op.kind == prg.OP_CONV else o.win).lens = self.lens.data_ptr()
-            if op.kind == prg.OP_CONV:
-                d = o.conv
-                for f in ("src0", "src1", "xf0", "xf1", "slope0", "slope1", "w", "bias", "aux", "dst", "dst_acc",
-                          "stats", "stat_slope0", "stat_slope1", "fin_stats", "fin_gamma0", "fin_beta0",
-                          "fin_gamma1", "fin_beta1", "fz_counter", "fz_gamma0", "fz_beta0", "fz_xf0", "fz_gamma1", "fz_beta1",
-                          "fz_xf1"):
-                    setattr(d, f, A(getattr(op, f)))
-                d.fz_eps = float(op.fz_eps)
-                for f in ("C0", "C1", "xf_mode", "N", "Kpad", "B", "T", "Fin", "Fout", "No", "ostride", "ophase",
-                          "istride", "epi", "Cout", "nsets", "stat_tiles", "stat_tile0", "bm", "fin_tiles",
-                          "fin_nsets", "fin_count", "precision", "korder", "p2_mask1"):
-                    setattr(d, f, int(getattr(op, f)))
-                d.fin_eps = float(op.fin_eps)
-                d.ntaps = len(op.dt)
-                for j in range(_lib.MAX_TAPS):
-                    d.dt[j] = op.dt[j] if j < len(op.dt) else 0
-                    d.ioff[j] = op.ioff[j] if j < len(op.ioff) else 0
-                # second output-column phase served by the same launch (small-tile kernel only)
-                d.ph1_w = A(op.ph1_w)
-                d.ph1_No, d.ph1_ophase, d.ph1_Kpad, d.ph1_ntaps = int(op.ph1_No), int(op.ph1_ophase), int(op.ph1_Kpad), len(op.ph1_dt)
-                for j in range(_lib.MAX_TAPS):
-                    d.ph1_dt[j] = op.ph1_dt[j] if j < len(op.ph1_dt) else 0
-                    d.ph1_ioff[j] = op.ph1_ioff[j] if j < len(op.ph1_ioff) else 0
-                # fused second 1x1 convolution (out_conv of one S-TCM + in_conv of the next)
-                for f in ("f2_w", "f2_dst", "f2_stats", "f2_stat_slope0", "f2_stat_slope1"):
-                    setattr(d, f, A(getattr(op, f)))
-                d.f2_N, d.f2_nsets, d.f2_stat_tiles = int(op.f2_N), int(op.f2_nsets), int(op.f2_stat_tiles)
-            elif op.kind == prg.OP_IN_FINALIZE:
-                o.i[0:5] = [op.B, op.C, op.nsets, op.stat_tiles, op.count]
-                o.f[0] = op.eps
-                for j, r in enumerate((op.stats, op.gamma0, op.beta0, op.xf0, op.gamma1, op.beta1, op.xf1)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_NORM_ACT:
-                o.i[0:4] = [op.B, op.P, op.C, op.T]
-                for j, r in enumerate((op.a, op.xfa, op.slopea, op.b, op.xfb, op.slopeb, op.out)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_LSTM64:
-                o.i[0:4] = [op.B, op.T, op.F, op.precision]
-                o.f[0] = op.ln_eps
-                for j, r in enumerate((op.x, op.ln_g, op.ln_b, op.wcat, op.bias, op.h_out, op.c_state)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_BFW_FS:
-                o.i[0:4] = [op.B, op.T, op.F, op.M]
-                for j, r in enumerate((op.y1, op.w2, op.b2, op.x, op.out, op.bfw, op.w1, op.b1)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_MEMSET0:
-                nbytes = 4 * op.nfloats
-                o.i[0] = C.c_int32(nbytes & 0xFFFFFFFF).value
-                o.i[1] = nbytes >> 32
-                o.i[2:5] = [op.B, op.T, op.row]
-                o.p[0] = A(op.ptr)
-            elif op.kind == prg.OP_CLN_STATS:
-                o.i[0:4] = [op.B, op.T, op.P, op.C]
-                o.f[0] = op.eps
-                for j, r in enumerate((op.x, op.slope, op.sums, op.state, op.mr)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_CLN_APPLY:
-                o.i[0:5] = [op.B, op.T, op.P, op.C, op.mode]
-                for j, r in enumerate((op.x, op.mr, op.gain, op.bias, op.slope, op.add, op.out)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_GATE_ROWS:
-                o.i[0:3] = [op.B, op.T, op.row]
-                for j, r in enumerate((op.a, op.r, op.z)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_GAG_PACK:
-                o.i[0:4] = [op.B, op.T, op.F, prg.GAG_PRE_LD]
-                for j, r in enumerate((op.inpt, op.pre_x, op.enc_in, op.pre)):
-                    o.p[j] = A(r)
-            elif op.kind == prg.OP_GAG_CRM:
-                o.i[0:6] = [op.B, op.T, op.F, prg.GAG_PRE_LD, prg.GAG_LIN_LD, op.act]
-                for j, r in enumerate((op.pre, op.g, op.r, op.i, op.pre_out, op.planar)):
-                    o.p[j] = A(r)
-            else:
-                raise ValueError(op.kind)
-        self._in_ptr, self._out_ptr = (in_ptr, out_ptr, in2_ptr), None
+    def bind(self, in_ptr: int, out_ptr: int, in2_ptr: Optional[int] = None) -> bool:
+        if not super().bind(in_ptr, out_ptr, in2_ptr):
+            return False
         self._plan_chains()
+        return True
+
+    def buffers(self, use_graph: bool, in_shape, out_shape, in2_shape=None):
+        """(in, out, in2), launch: boundary buffers the program is bound to and the call that runs it on them -- the
+        captured form's static buffers and its replay, or (use_graph False, or the capture refused) fresh zero-filled
+        buffers and direct launches on torch's current stream.  in2 is None without in2_shape."""
+        if use_graph and self.capture(in_shape, out_shape, in2_shape):
+            return (self.static_in, self.static_out, self.static_in2), self.graph.replay
+        bufs = tuple(None if s is None else torch.zeros(s, dtype=torch.float32, device=self.device)
+                     for s in (in_shape, out_shape, in2_shape))
+        self.bind(*(None if b is None else b.data_ptr() for b in bufs))
+        return bufs, lambda: self.run(torch.cuda.current_stream().cuda_stream)
 
     def _plan_chains(self) -> None:
         """Streaming programs: runs of consecutive small-tile convolutions that give every utterance ONE tile (the S-TCN of a
@@ -332,30 +227,15 @@ class _Bound:
         self.exec_ops = (_lib.Op * len(exec_list))(*exec_list)
         self.n_exec = len(exec_list)
 
-    def _launch(self, stream: int, first: int, n: int) -> None:
-        if first == 0 and n == len(self.prog.ops) and getattr(self, "exec_ops", None) is not None:
+    def _launch(self, name: str, stream: int, first: int, n: int) -> None:
+        if first == 0 and n == len(self.prog.ops) and self.exec_ops is not None:
             _lib.check(_lib.load().eab_run_program(self.exec_ops, self.n_exec, C.c_void_p(stream)), "eab_run_program")
             return
-        ops = C.cast(C.byref(self.ops, first * C.sizeof(_lib.Op)), C.POINTER(_lib.Op))
-        _lib.check(_lib.load().eab_run_program(ops, n, C.c_void_p(stream)), "eab_run_program")
-
-    def _plan(self) -> list:
-        n = len(self.prog.ops)
-        if self.prog.sync and graph_branches_allowed():
-            return plan_segments(n, self.prog.lanes, self.prog.sync)
-        return single_lane(n)
+        super()._launch(name, stream, first, n)
 
     def run(self, stream: int, first: int = 0, count: Optional[int] = None) -> None:
-        """Enqueue ops [first, first+count) on ``stream`` (a raw hipStream_t) with direct kernel launches.  Whole programs
-        with parallel branches (prog.sync) fork onto side streams with events, exactly as their captured form replays
-        (graphs.LaneGraphs)."""
-        n = len(self.prog.ops) - first if count is None else count
-        if not self.prog.sync or count is not None or not graph_branches_allowed():
-            return self._launch(stream, first, n)         # single lane (or a single-op debug launch)
-        assert torch.cuda.current_stream().cuda_stream == stream, "multi-lane programs run on torch's current stream"
-        if getattr(self, "_direct", None) is None:
-            self._direct = LaneGraphs(self.device, self._plan(), self._launch)
-        self._direct.run_direct()
+        """Enqueue ops [first, first+count) on ``stream`` (a raw hipStream_t) with direct kernel launches (BoundProgram.run)."""
+        super().run("run", stream, first, count)
 
     def view(self, act: prg.Act) -> torch.Tensor:
         """Debug view of a named activation as (B, T, F, C)."""
@@ -368,15 +248,6 @@ class _Bound:
 # ----------------------------------------------------------------------------
 # the module
 # ----------------------------------------------------------------------------
-def graph_branches_allowed() -> bool:
-    """Parallel branches (side streams) for programs that mark independent chains?  EAB_GRAPH_BRANCHES=0 runs every program
-    on one stream.  (Rounds 1-3 also switched them off while a torch.distributed process group was alive: a hipGraph with
-    internal branches could crash the HIP runtime at replay.  The cause is an unchecked index in the runtime's stream
-    assignment, graphs.py; since branches replay as separate single-stream graphs the condition no longer exists.)"""
-    import os
-    return os.environ.get("EAB_GRAPH_BRANCHES", "1") != "0"
-
-
 AUTO_BUCKETS = tuple(64 << k for k in range(8))          # length_buckets="auto": 64, 128, .., 8192 frames
 
 
@@ -427,7 +298,7 @@ class _HipModule(nn.Module):
         for key, spec in specs.items():
             t = _default_init(spec)
             _attach(self, key, t if spec.is_buffer else nn.Parameter(t))
-        self._bound: Dict[tuple, _Bound] = {}
+        self._bound: "OrderedDict[tuple, _Bound]" = OrderedDict()
         self._packed_version: Dict[tuple, tuple] = {}
         self.dump_bfw = False                         # tests: also emit the (B,T,F,M,2) beam-forming weights
         # replay the lowered program as ONE hipGraph launch (static internal in/out buffers, one
@@ -474,22 +345,30 @@ class _HipModule(nn.Module):
         return {k: sd[k].detach().to("cpu", torch.float32).numpy() for k, s in self._specs.items()
                 if s.kind != "bn_count"}
 
-    def _program(self, B: int, T: int, F: int, device: torch.device) -> _Bound:
+    def _program(self, B: int, T: int, F: int, device: torch.device, varlen: bool = False) -> _Bound:
+        """The bound program of (B, T, F) on ``device``, its packed weights current.  Exact-shape programs keep one shape
+        resident (activations can be GBs); length-bucketed (varlen) ones live in an LRU bounded by max_resident_programs
+        and max_resident_bytes."""
         chains = bool(self.__dict__.get("parallel_chains", True))
         key = (B, T, F, str(device), self.precision, chains)
+        cache, versions = (self._varlen_bound, self._varlen_version) if varlen else (self._bound, self._packed_version)
+        limit, budget = (self.max_resident_programs, self.max_resident_bytes) if varlen else (1, math.inf)
         fp = self._param_fingerprint()
-        bound = self._bound.get(key)
-        if bound is None or ("bf_w" in bound.prog.taps) != self.dump_bfw:
-            prog = prg.lower(self.cfg, self._numpy_params(), B, T, F, dump_bfw=self.dump_bfw,
-                             precision=self.precision, parallel_chains=chains)
-            bound = _Bound(prog, device)
-            self._bound = {key: bound}                # keep one shape resident (activations can be GBs)
-            self._packed_version = {key: fp}
-        elif self._packed_version.get(key) != fp:
-            prog = prg.lower(self.cfg, self._numpy_params(), B, T, F, dump_bfw=self.dump_bfw,
-                             precision=self.precision, parallel_chains=chains)
-            bound.update_weights(prog.weights)
-            self._packed_version[key] = fp
+        bound = cache.get(key)
+        stale = bound is None or ("bf_w" in bound.prog.taps) != self.dump_bfw
+        if stale or versions.get(key) != fp:
+            prog = prg.lower(self.cfg, self._numpy_params(), B, T, F, dump_bfw=self.dump_bfw, precision=self.precision,
+                             parallel_chains=chains, varlen=varlen)
+            if stale:
+                need = 4 * max(prog.act_floats, 1)
+                while cache and (len(cache) >= limit or sum(4 * b.acts.numel() for b in cache.values()) + need > budget):
+                    old, _ = cache.popitem(last=False)            # least recently used
+                    versions.pop(old, None)
+                bound = cache[key] = _Bound(prog, device)
+            else:
+                bound.update_weights(prog.weights)
+            versions[key] = fp
+        cache.move_to_end(key)
         return bound
 
     # -- per-utterance lengths / length buckets ----------------------------------------
@@ -528,69 +407,75 @@ class _HipModule(nn.Module):
         cap = bucket_for(T, self._bucket_caps()) if self.length_buckets is not None else None
         return (cap if cap is not None else T), lens
 
-    def _varlen_program(self, B: int, T_cap: int, F: int, device: torch.device) -> _Bound:
-        chains = bool(self.__dict__.get("parallel_chains", True))
-        key = (B, T_cap, F, str(device), self.precision, chains)
-        fp = self._param_fingerprint()
-        bound = self._varlen_bound.get(key)
-        if bound is None:
-            prog = prg.lower(self.cfg, self._numpy_params(), B, T_cap, F, precision=self.precision,
-                             parallel_chains=chains, varlen=True)
-            need = 4 * max(prog.act_floats, 1)
-            while self._varlen_bound and (len(self._varlen_bound) >= self.max_resident_programs or
-                                          sum(4 * b.acts.numel() for b in self._varlen_bound.values()) + need
-                                          > self.max_resident_bytes):
-                old, _ = self._varlen_bound.popitem(last=False)            # least recently used
-                self._varlen_version.pop(old, None)
-            bound = _Bound(prog, device)
-            self._varlen_bound[key] = bound
-            self._varlen_version[key] = fp
-        elif self._varlen_version.get(key) != fp:
-            prog = prg.lower(self.cfg, self._numpy_params(), B, T_cap, F, precision=self.precision,
-                             parallel_chains=chains, varlen=True)
-            bound.update_weights(prog.weights)
-            self._varlen_version[key] = fp
-        self._varlen_bound.move_to_end(key)
-        return bound
-
     def varlen_arena_bytes(self) -> Dict[tuple, int]:
         """Activation-arena bytes of every resident length-bucketed program, keyed (B, T_cap, F, device, precision, chains)."""
         return {k: 4 * b.acts.numel() for k, b in self._varlen_bound.items()}
 
-    def _run_varlen(self, T_cap: int, lens, inputs, out_shape) -> Tuple[_Bound, torch.Tensor]:
-        """Run the per-utterance-length program of cap T_cap on ``inputs`` (time axis 1 for EaBNet's (B,T,F,M,2), 2 for
-        GaGNet's (B,2,T,F)); returns the full (.., T_cap, ..) output buffer.  The lengths reach the device array on the
-        launch stream (pinned host copy or device-to-device), with no host synchronisation."""
-        x0 = inputs[0]
-        tax = 1 if x0.ndim == 5 else 2
-        B, T = x0.shape[0], x0.shape[tax]
-        F = x0.shape[-1] if tax == 2 else x0.shape[2]
-        bound = self._varlen_program(B, T_cap, F, x0.device)
-        if isinstance(lens, int):
-            bound.lens.fill_(lens)
-        elif isinstance(lens, torch.Tensor) and lens.is_cuda:
-            bound.lens.copy_(lens.to(torch.int32), non_blocking=True)
-        else:
-            bound.lens.copy_(torch.as_tensor(lens, dtype=torch.int32).pin_memory(), non_blocking=True)
-        pad = lambda t: tuple(t.shape[:tax]) + (T_cap,) + tuple(t.shape[tax + 1:])  # noqa: E731
-        cap_out = tuple(out_shape[:-2]) + (T_cap, out_shape[-1])
-        in2 = pad(inputs[1]) if len(inputs) > 1 else None
-        if self.use_graph and not torch.cuda.is_current_stream_capturing() and bound.capture(pad(x0), cap_out, in2):
-            stat = [bound.static_in] + ([bound.static_in2] if in2 else [])
-            for dst, src in zip(stat, inputs):
-                dst.narrow(tax, 0, T).copy_(src, non_blocking=True)
-            bound.graph.replay()
-            return bound, bound.static_out
-        stat = []
-        for src in inputs:
-            buf = torch.zeros(pad(src), dtype=torch.float32, device=src.device)
-            buf.narrow(tax, 0, T).copy_(src)
-            stat.append(buf)
-        out = torch.empty(cap_out, dtype=torch.float32, device=x0.device)
-        bound.bind(stat[0].data_ptr(), out.data_ptr(), stat[1].data_ptr() if len(stat) > 1 else None)
-        bound.run(torch.cuda.current_stream().cuda_stream)
-        self._last_varlen = stat
-        return bound, out
+    def _forward(self, inputs: tuple, out_shape: tuple, tax: int, lengths) -> torch.Tensor:
+        """The forward of either network: ``inputs`` with the time axis ``tax`` -> its output arena of ``out_shape``
+        ((B, 2, T, F) or (q, B, 2, T, F)), fp32.  Differentiable calls run the training programs, the
+        others the exact-shape program or, with lengths= or length buckets, a per-utterance-length program."""
+        x0, name = inputs[0], type(self).__name__
+        noun = "input" if len(inputs) == 1 else "inputs"
+        B, T, F = x0.shape[0], x0.shape[tax], x0.shape[tax + 1]
+        needs_graph = self._needs_graph(*inputs)
+        vl = self._varlen_call(T, B, lengths, needs_graph)
+        if needs_graph:
+            # training: forward AND backward on the hand-written kernels (train.py: two static op programs behind one
+            # autograd node) for every supported configuration; BatchNorm = train mode (batch statistics + buffer update)
+            from . import train
+            if not (all(x.is_cuda for x in inputs) and next(self.parameters()).is_cuda):
+                raise _lib.EabError(f"eabnet_amd.{name} trains on MI355X only: move the {noun} and the module to 'cuda'. "
+                                    "There is no CPU fallback by design.")
+            if any(x.requires_grad for x in inputs):
+                raise _refuse_differentiable(self, *self._input_grad_refusal)
+            if self.norm_type == "BN" and not self.training:
+                raise _refuse_differentiable(self, "BatchNorm in eval mode under autograd", "the training programs implement "
+                                             "BatchNorm's train mode; call .train(), or torch.no_grad() for inference")
+            lower = self._training_lowering()
+            self.training_backend = "hip"
+            xs = tuple(x.detach().to(torch.float32).contiguous() for x in inputs)
+            return train.forward_train(self, xs, lower)
+        if not all(x.is_cuda for x in inputs):
+            raise _lib.EabError(f"eabnet_amd.{name} inference runs on MI355X only: move the {noun} (and module) to "
+                                "'cuda'. There is no CPU fallback by design.")
+        _lib.load()
+        xs = tuple(x.detach().to(torch.float32) for x in inputs)
+        use_graph = self.use_graph and not self.dump_bfw and not torch.cuda.is_current_stream_capturing()
+        with torch.cuda.device(x0.device):
+            if vl is None:
+                xs = tuple(x.contiguous() for x in xs)
+                bound = self._program(B, T, F, x0.device)
+                if use_graph and bound.capture(xs[0].shape, out_shape, xs[1].shape if len(xs) > 1 else None):
+                    for buf, x in zip((bound.static_in, bound.static_in2), xs):
+                        buf.copy_(x, non_blocking=True)
+                    bound.graph.replay()
+                    out = bound.static_out.clone()
+                else:
+                    out = torch.empty(out_shape, dtype=torch.float32, device=x0.device)
+                    bound.bind(xs[0].data_ptr(), out.data_ptr(), xs[1].data_ptr() if len(xs) > 1 else None)
+                    bound.run(torch.cuda.current_stream().cuda_stream)
+            else:
+                # per-utterance lengths: the program of cap T_cap, the lengths written to its device array on the launch
+                # stream (pinned host copy or device-to-device, no host synchronisation), the inputs into its padded buffers
+                T_cap, lens = vl
+                bound = self._program(B, T_cap, F, x0.device, varlen=True)
+                if isinstance(lens, int):
+                    bound.lens.fill_(lens)
+                elif isinstance(lens, torch.Tensor) and lens.is_cuda:
+                    bound.lens.copy_(lens.to(torch.int32), non_blocking=True)
+                else:
+                    bound.lens.copy_(torch.as_tensor(lens, dtype=torch.int32).pin_memory(), non_blocking=True)
+                pad = lambda shp, ax: tuple(shp[:ax]) + (T_cap,) + tuple(shp[ax + 1:])  # noqa: E731
+                (b_in, b_out, b_in2), launch = bound.buffers(use_graph, pad(xs[0].shape, tax), pad(out_shape, -2),
+                                                             pad(xs[1].shape, tax) if len(xs) > 1 else None)
+                for buf, x in zip((b_in, b_in2), xs):
+                    buf.narrow(tax, 0, T).copy_(x, non_blocking=True)
+                launch()
+                out = b_out[..., :T, :].clone()
+                self._last_varlen = (b_in, b_out, b_in2)          # direct launches: keep the buffers alive
+        self._last = (bound, *xs)                     # keep the inputs alive until the stream has consumed them
+        return out
 
     # -- streaming ------------------------------------------------------------------
     def stream_begin(self, B: int, T_max: int, chunk: int = 1, F: int = 161, device=None) -> EaBNetStream:
@@ -655,61 +540,21 @@ class EaBNet(_HipModule):
             inpt = inpt.unsqueeze(-2)
         if inpt.ndim != 5 or inpt.shape[-1] != 2 or inpt.shape[-2] != self.M:
             raise ValueError(f"expected (B,T,F,{self.M},2), got {tuple(inpt.shape)}")
-        vl = self._varlen_call(inpt.shape[1], inpt.shape[0], lengths, self._needs_graph(inpt))
-        if vl is not None:
-            if not inpt.is_cuda:
-                raise _lib.EabError("eabnet_amd.EaBNet inference runs on MI355X only: move the input (and module) to 'cuda'.")
-            _lib.load()
-            B, T, F, M, _ = inpt.shape
-            x = inpt.detach().to(torch.float32)
-            with torch.cuda.device(x.device):
-                bound, full = self._run_varlen(vl[0], vl[1], (x,), (B, 2, T, F))
-                out = full[:, :, :T].clone()
-            self._last = (bound, x)
-            if self.topo_type == "miso":
-                out = out.sum(dim=-1)
-            return out.to(inpt.dtype)
-        if self._needs_graph(inpt):
-            # training: forward AND backward on the hand-written kernels (train.py: two static op programs behind one
-            # autograd node) for every constructor branch; BatchNorm = train mode (batch statistics + buffer update)
-            from . import train
-            if not (inpt.is_cuda and next(self.parameters()).is_cuda):
-                raise _lib.EabError("eabnet_amd.EaBNet trains on MI355X only: move the input and the module to 'cuda'. "
-                                    "There is no CPU fallback by design.")
-            if inpt.requires_grad:
-                raise _refuse_differentiable(self, "the input requires grad", "the training programs produce parameter "
-                                             "gradients only, as the reference's training loop needs")
-            if self.norm_type == "BN" and not self.training:
-                raise _refuse_differentiable(self, "BatchNorm in eval mode under autograd", "the training programs implement "
-                                             "BatchNorm's train mode; call .train(), or torch.no_grad() for inference")
-            if not train.supported(self.cfg):
-                raise _refuse_differentiable(self, "topology outside the training programs", train.unsupported_reason(self.cfg))
-            self.training_backend = "hip"
-            out = train.forward_train(self, inpt)
-            return out.sum(dim=-1) if self.topo_type == "miso" else out      # (EaBNet.py:122-123, as in inference below)
-        if not inpt.is_cuda:
-            raise _lib.EabError("eabnet_amd.EaBNet inference runs on MI355X only: move the input (and module) to "
-                                "'cuda'. There is no CPU fallback by design.")
-        _lib.load()
-        B, T, F, M, _ = inpt.shape
-        x = inpt.detach().to(torch.float32).contiguous()
-        with torch.cuda.device(x.device):
-            bound = self._program(B, T, F, x.device)
-            if self.use_graph and not self.dump_bfw and not torch.cuda.is_current_stream_capturing() \
-                    and bound.capture((B, T, F, M, 2), (B, 2, T, F)):
-                bound.static_in.copy_(x, non_blocking=True)
-                bound.graph.replay()
-                out = bound.static_out.clone()
-            else:
-                out = torch.empty((B, 2, T, F), dtype=torch.float32, device=x.device)
-                bound.bind(x.data_ptr(), out.data_ptr())
-                bound.run(torch.cuda.current_stream().cuda_stream)
-        self._last = (bound, x)                       # keep the input alive until the stream has consumed it
+        out = self._forward((inpt,), (inpt.shape[0], 2, inpt.shape[1], inpt.shape[2]), 1, lengths)
         if self.topo_type == "miso":
             # the reference reduces the masked reference-mic spectrum over frequency (EaBNet.py:122-123:
             # ``.sum(dim=-1)`` on a (B,T,F) tensor) and returns (B,2,T); kept as is
             out = out.sum(dim=-1)
         return out.to(inpt.dtype)
+
+    _input_grad_refusal = ("the input requires grad", "the training programs produce parameter gradients only, as the "
+                           "reference's training loop needs")
+
+    def _training_lowering(self):
+        from . import train
+        if not train.supported(self.cfg):
+            raise _refuse_differentiable(self, "topology outside the training programs", train.unsupported_reason(self.cfg))
+        return train.lower_train
 
 
 class EaBNetStream:
@@ -732,13 +577,7 @@ class EaBNetStream:
             in_shape, out_shape, in2_shape = (B, 2, T_max, F), (net.q, B, 2, T_max, F), (B, 2, T_max, F)
         else:
             in_shape, out_shape, in2_shape = (B, T_max, F, net.M, 2), (B, 2, T_max, F), None
-        if not (net.use_graph and bound.capture(in_shape, out_shape, in2_shape)):
-            self._in = torch.zeros(in_shape, dtype=torch.float32, device=bound.device)
-            self._out = torch.zeros(out_shape, dtype=torch.float32, device=bound.device)
-            self._in2 = torch.zeros(in2_shape, dtype=torch.float32, device=bound.device) if in2_shape else None
-            bound.bind(self._in.data_ptr(), self._out.data_ptr(), self._in2.data_ptr() if in2_shape else None)
-        else:
-            self._in, self._out, self._in2 = bound.static_in, bound.static_out, bound.static_in2
+        (self._in, self._out, self._in2), self._launch = bound.buffers(net.use_graph, in_shape, out_shape, in2_shape)
 
     def reset(self) -> None:
         """Start a new batch of utterances (no buffer needs clearing: position 0 ignores all state)."""
@@ -769,10 +608,7 @@ class EaBNetStream:
                 if n < self.chunk and end > hi:       # rows the kernels touch beyond the new frames must be defined
                     buf.narrow(tdim, hi, min(end, self.T_max) - hi).zero_()
             self.bound.t_pos.fill_(lo)
-            if self.bound.graph is not None:
-                self.bound.graph.replay()
-            else:
-                self.bound.run(torch.cuda.current_stream().cuda_stream)
+            self._launch()
             out = self._out[..., lo:hi, :].clone()
         self.pos += n
         self._closed = n < self.chunk
@@ -791,7 +627,7 @@ def _replica(module: nn.Module) -> nn.Module:
     rep = copy.copy(module)
     rep._modules = {k: (_replica(v) if v is not None else None) for k, v in module._modules.items()}
     if isinstance(rep, _HipModule):
-        rep._bound, rep._packed_version = {}, {}
+        rep._bound, rep._packed_version = OrderedDict(), {}
         # the Pipeline serves exact shapes (its replicas own their programs; length buckets stay with the original module)
         rep.length_buckets, rep._varlen_bound, rep._varlen_version = None, OrderedDict(), {}
         rep.__dict__.pop("_slot_list", None)
@@ -1011,59 +847,18 @@ class GaGNet(_HipModule):
         :return: list of q estimates (B, 2, F, T)   (reference GaGNet.py:76-90)"""
         if inpt.ndim != 4 or inpt.shape[1] != 2 or inpt.shape[3] != self.cfg.freq or pre_x.shape != inpt.shape:
             raise ValueError(f"expected two (B,2,T,{self.cfg.freq}) tensors, got {tuple(inpt.shape)} and {tuple(pre_x.shape)}")
-        vl = self._varlen_call(inpt.shape[2], inpt.shape[0], lengths, self._needs_graph(inpt, pre_x))
-        if vl is not None:
-            if not (inpt.is_cuda and pre_x.is_cuda):
-                raise _lib.EabError("eabnet_amd.GaGNet inference runs on MI355X only: move the inputs (and module) to 'cuda'.")
-            _lib.load()
-            B, _, T, F = inpt.shape
-            a = inpt.detach().to(torch.float32)
-            b = pre_x.detach().to(torch.float32)
-            with torch.cuda.device(a.device):
-                bound, full = self._run_varlen(vl[0], vl[1], (a, b), (self.q, B, 2, T, F))
-                out = full[:, :, :, :T].clone()
-            self._last = (bound, a, b)
-            out = out.to(inpt.dtype)
-            return [out[j].permute(0, 1, 3, 2) for j in range(self.q)]
-        if self._needs_graph(inpt, pre_x):
-            # training: forward AND backward on the hand-written kernels (train_gag.py).  No gradient flows to the inputs:
-            # the reference feeds the detached beam-former estimate (EaBNet.py:142)
-            from . import train_gag
-            if not (inpt.is_cuda and pre_x.is_cuda and next(self.parameters()).is_cuda):
-                raise _lib.EabError("eabnet_amd.GaGNet trains on MI355X only: move the inputs and the module to 'cuda'. "
-                                    "There is no CPU fallback by design.")
-            if inpt.requires_grad or pre_x.requires_grad:
-                raise _refuse_differentiable(self, "an input requires grad", "the reference detaches the beam-former's estimate, "
-                                             "EaBNet.py:142; the training programs produce parameter gradients only")
-            if self.norm_type == "BN" and not self.training:
-                raise _refuse_differentiable(self, "BatchNorm in eval mode under autograd", "the training programs implement "
-                                             "BatchNorm's train mode; call .train(), or torch.no_grad() for inference")
-            if not train_gag.supported(self.cfg):
-                raise _refuse_differentiable(self, "post-filter topology outside the training programs", "see train_gag.supported")
-            self.training_backend = "hip"
-            return train_gag.forward_train(self, inpt, pre_x)
-        if not (inpt.is_cuda and pre_x.is_cuda):
-            raise _lib.EabError("eabnet_amd.GaGNet inference runs on MI355X only: move the inputs (and module) to "
-                                "'cuda'. There is no CPU fallback by design.")
-        _lib.load()
-        B, _, T, F = inpt.shape
-        a = inpt.detach().to(torch.float32).contiguous()
-        b = pre_x.detach().to(torch.float32).contiguous()
-        with torch.cuda.device(a.device):
-            bound = self._program(B, T, F, a.device)
-            if self.use_graph and not torch.cuda.is_current_stream_capturing() \
-                    and bound.capture((B, 2, T, F), (self.q, B, 2, T, F), (B, 2, T, F)):
-                bound.static_in.copy_(a, non_blocking=True)
-                bound.static_in2.copy_(b, non_blocking=True)
-                bound.graph.replay()
-                out = bound.static_out.clone()
-            else:
-                out = torch.empty((self.q, B, 2, T, F), dtype=torch.float32, device=a.device)
-                bound.bind(a.data_ptr(), out.data_ptr(), b.data_ptr())
-                bound.run(torch.cuda.current_stream().cuda_stream)
-        self._last = (bound, a, b)
-        out = out.to(inpt.dtype)
+        out = self._forward((inpt, pre_x), (self.q,) + tuple(inpt.shape), 2, lengths).to(inpt.dtype)
         return [out[j].permute(0, 1, 3, 2) for j in range(self.q)]
+
+    # no gradient flows to the inputs: the reference feeds the detached beam-former estimate (EaBNet.py:142)
+    _input_grad_refusal = ("an input requires grad", "the reference detaches the beam-former's estimate, EaBNet.py:142; the "
+                           "training programs produce parameter gradients only")
+
+    def _training_lowering(self):
+        from . import train_gag
+        if not train_gag.supported(self.cfg):
+            raise _refuse_differentiable(self, "post-filter topology outside the training programs", "see train_gag.supported")
+        return train_gag.lower_train
 
 
 def make_gag_net(args) -> GaGNet:

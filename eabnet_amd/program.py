@@ -33,8 +33,9 @@ XF_NONE, XF_NORM_PRELU, XF_PRELU_NORM = 0, 1, 2
 EPI_LINEAR, EPI_GLU, EPI_RELU, EPI_MULSIG, EPI_ADD, EPI_DUALGATE, EPI_PHASE2 = 0, 1, 2, 3, 4, 5, 6
 OP_CONV, OP_IN_FINALIZE, OP_NORM_ACT, OP_LSTM64, OP_BFW_FS, OP_MEMSET0, OP_GAG_PACK, OP_GAG_CRM = 1, 2, 3, 4, 5, 6, 7, 8
 OP_CLN_STATS, OP_CLN_APPLY, OP_GATE_ROWS = 33, 34, 35
-OP_CLN_STEP = 38         # run-time only (model._Bound): statistics + apply of a cLN unit for a one-frame streaming step in one launch
-OP_CONV_CHAIN = 9        # run-time only (model._Bound): a run of small-tile launches executed by one launch (csrc/conv_st.hip)
+OP_CLN_STEP = 38         # run-time only (model._Bound._plan_chains): statistics + apply of a cLN unit for a one-frame streaming step in one launch
+OP_CONV_CHAIN = 9        # run-time only (model._Bound._plan_chains): a run of small-tile launches executed by one launch (csrc/conv_st.hip)
+OP_WGRAD = 32            # training only (train.WgradOp): weight gradient of a convolution
 ACT_SIGMOID, ACT_TANH, ACT_RELU = 0, 1, 2
 GAG_PRE_LD = 324   # floats per (b, t) row of the interleaved previous estimate: 2*161 rounded up to a float4
 GAG_LIN_LD = 192   # 161 linear outputs padded to three 64-column tiles
@@ -151,6 +152,9 @@ class ConvOp:
     f2_stat_tiles: int = 0
     # EPI_PHASE2: bit j = tap j also feeds the phase-1 columns (eab_conv_desc.p2_mask1)
     p2_mask1: int = 0
+    # training programs (train.py): GLU factor dump for the backward, bf16-stored sources (eab_conv_desc.glu_dump / src_bf16)
+    glu_dump: Optional[Ref] = None
+    src_bf16: int = 0
 
 
 @dataclass
@@ -168,6 +172,7 @@ class FinalizeOp:
     gamma1: Optional[Ref] = None
     beta1: Optional[Ref] = None
     xf1: Optional[Ref] = None
+    mr0: Optional[Ref] = None            # training programs: (mean, rstd) table for the backward
     name: str = ""
     kind: int = OP_IN_FINALIZE
 

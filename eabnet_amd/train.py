@@ -37,13 +37,14 @@ import torch
 
 from . import _lib
 from . import program as prg
-from .graphs import LaneGraphs, plan_segments, single_lane
+from .runtime import BoundProgram
 from .program import ALIGN, EPS_IN, EPS_LN, Ref, conv_tiles, glu_row_order
 from .spec import NetConfig, gate_key, param_specs
 
 XF_NORM_PRELU, XF_PRELU_NORM = prg.XF_NORM_PRELU, prg.XF_PRELU_NORM
 (OP_GATHER, OP_IN_STATS, OP_TR_NORM_ACT, OP_NORM_BWD, OP_GLU_BWD, OP_GATE_FWD, OP_GATE_BWD, OP_ADD, OP_RELU_BWD, OP_COLSUM,
- OP_FILTER_SUM, OP_FS_BWD, OP_LN_FWD, OP_LN_BWD, OP_LSTM_TRAIN, OP_LSTM_BWD, OP_WGRAD) = range(16, 33)
+ OP_FILTER_SUM, OP_FS_BWD, OP_LN_FWD, OP_LN_BWD, OP_LSTM_TRAIN, OP_LSTM_BWD) = range(16, 32)
+OP_WGRAD = prg.OP_WGRAD
 OP_CLN_STATS, OP_CLN_APPLY, OP_CLN_BWD = prg.OP_CLN_STATS, prg.OP_CLN_APPLY, 37      # include/eabnet_hip.h EAB_OP_CLN_*
 NB_SUMS_ZEROED = 0x100   # include/eabnet_hip.h EAB_NB_SUMS_ZEROED
 NB_SUM_COPIES = 8        # include/eabnet_hip.h EAB_NB_SUM_COPIES: the reduce pass spreads its atomics over that many copies
@@ -1035,145 +1036,22 @@ def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "
 # ----------------------------------------------------------------------------------------------------------------
 # binding and execution
 # ----------------------------------------------------------------------------------------------------------------
-class TrainBound:
-    """Device arenas + the two ctypes op arrays of a lowered training program."""
+class TrainBound(BoundProgram):
+    """Device arenas + the forward ("fwd") and backward ("bwd") op lists of a lowered training program."""
+    BOUNDARY = ("in", "out", "dout", "in2")
 
     def __init__(self, prog: TrainProgram, device: torch.device):
-        self.prog, self.device = prog, device
+        self.prog = prog
         self.acts = torch.empty(max(prog.a_floats, 1), dtype=torch.float32, device=device)
         self.w = torch.empty(max(prog.w_floats, 1), dtype=torch.float32, device=device)
         self.g = torch.empty(max(prog.g_floats, 1), dtype=torch.float32, device=device)
+        super().__init__(device, {"a": self.acts, "w": self.w, "g": self.g}, {"fwd": prog.fwd, "bwd": prog.bwd},
+                         prog.lanes, prog.sync)
         self.ia = torch.from_numpy(prog.ia).to(device)
         self.ib = torch.from_numpy(prog.ib).to(device) if prog.ib is not None else None
         self.inv = torch.from_numpy(prog.inv).to(device)
-        self.fwd = (_lib.Op * len(prog.fwd))()
-        self.bwd = (_lib.Op * len(prog.bwd))()
-        self._bound = None
         self.serial = 0                     # forward passes run so far: a backward must belong to the latest one
         self.use_graph = True
-        self.graphs = None                  # (forward hipGraph, backward hipGraph) on the static boundary buffers
-        self.graph_failed = False
-        self.static_x = self.static_x2 = self.static_out = self.static_dout = None
-        self._direct = {}                   # which -> graphs.LaneGraphs for direct (uncaptured) multi-lane runs
-        self.parallel_branches = os.environ.get("EAB_TRAIN_BRANCHES", "1") != "0"      # A/B knob
-
-    def capture(self, x_shape) -> bool:
-        """Both programs as hipGraphs on static boundary buffers (input, output, output gradient): a step is two graph
-        launches instead of ~840 host-side kernel launches.  False (direct launches) if the runtime refuses."""
-        if self.graphs is not None or self.graph_failed or not self.use_graph:
-            return self.graphs is not None
-        prog = self.prog
-        try:
-            self.static_x = torch.zeros(x_shape, dtype=torch.float32, device=self.device)
-            self.static_x2 = torch.zeros(x_shape, dtype=torch.float32, device=self.device) if prog.has_in2 else None
-            self.static_out = torch.zeros(prog.out_shape or (prog.B, 2, prog.T, prog.F), dtype=torch.float32, device=self.device)
-            self.static_dout = torch.zeros_like(self.static_out)
-            self.bind(self.static_x.data_ptr(), self.static_out.data_ptr(), self.static_dout.data_ptr(),
-                      self.static_x2.data_ptr() if prog.has_in2 else None)
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                 # warm-up outside the capture (weights are packed already)
-                self.g.zero_()
-                self._launch("fwd", side.cuda_stream, 0, len(self.prog.fwd))       # (program order on one stream)
-                self._launch("bwd", side.cuda_stream, 0, len(self.prog.bwd))
-            torch.cuda.current_stream().wait_stream(side)
-            # one single-stream hipGraph per lane segment (graphs.py: a hipGraph with internal branches can crash the HIP
-            # runtime at replay); programs without parallel branches are one graph each
-            graphs = []
-            for which in ("fwd", "bwd"):
-                lg = LaneGraphs(self.device, self._plan(which), lambda st, first, count, w=which: self._launch(w, st, first, count))
-                lg.capture()
-                graphs.append(lg)
-            self.graphs = tuple(graphs)
-        except Exception as e:                            # noqa: BLE001 - any capture failure -> direct launches
-            import warnings
-            warnings.warn(f"eabnet_amd: hipGraph capture of the training programs failed ({e!r}); using direct launches")
-            self.graphs, self.graph_failed, self._bound = None, True, None
-        return self.graphs is not None
-
-    def bind(self, in_ptr: int, out_ptr: int, dout_ptr: int, in2_ptr: Optional[int] = None) -> None:
-        if self._bound == (in_ptr, out_ptr, dout_ptr, in2_ptr):
-            return
-        bases = {"a": self.acts.data_ptr(), "w": self.w.data_ptr(), "g": self.g.data_ptr(), "in": in_ptr, "out": out_ptr,
-                 "dout": dout_ptr, "in2": in2_ptr}
-
-        def A(r):
-            return None if r is None else bases[r.arena] + 4 * r.off
-        for ops, arr in ((self.prog.fwd, self.fwd), (self.prog.bwd, self.bwd)):
-            for k, op in enumerate(ops):
-                o = arr[k]
-                o.kind = op.kind
-                if op.kind == prg.OP_CONV:
-                    d = o.conv
-                    for f in ("src0", "src1", "xf0", "xf1", "slope0", "slope1", "w", "bias", "aux", "dst", "dst_acc", "stats",
-                              "stat_slope0", "stat_slope1", "fin_stats", "fin_gamma0", "fin_beta0", "fin_gamma1", "fin_beta1"):
-                        setattr(d, f, A(getattr(op, f)))
-                    d.glu_dump = A(getattr(op, "glu_dump", None))
-                    d.src_bf16 = int(getattr(op, "src_bf16", 0))
-                    for f in ("C0", "C1", "xf_mode", "N", "Kpad", "B", "T", "Fin", "Fout", "No", "ostride", "ophase", "istride",
-                              "epi", "Cout", "nsets", "stat_tiles", "stat_tile0", "bm", "fin_tiles", "fin_nsets", "fin_count",
-                              "precision", "korder"):
-                        setattr(d, f, int(getattr(op, f)))
-                    d.fin_eps = float(op.fin_eps)
-                    d.ntaps = len(op.dt)
-                    for j in range(_lib.MAX_TAPS):
-                        d.dt[j] = op.dt[j] if j < len(op.dt) else 0
-                        d.ioff[j] = op.ioff[j] if j < len(op.ioff) else 0
-                elif op.kind == prg.OP_IN_FINALIZE:
-                    o.i[0:5] = [op.B, op.C, op.nsets, op.stat_tiles, op.count]
-                    o.f[0] = op.eps
-                    for j, r in enumerate((op.stats, op.gamma0, op.beta0, op.xf0, op.gamma1, op.beta1, op.xf1,
-                                           getattr(op, "mr0", None), None)):
-                        o.p[j] = A(r)
-                elif op.kind == prg.OP_MEMSET0:
-                    nbytes = 4 * op.nfloats
-                    o.i[0] = C.c_int32(nbytes & 0xFFFFFFFF).value
-                    o.i[1] = nbytes >> 32
-                    o.p[0] = A(op.ptr)
-                elif op.kind == OP_WGRAD:
-                    d = o.wgrad
-                    d.dz, d.src0, d.src1, d.dw, d.dbias = A(op.dz), A(op.src0), A(op.src1), A(op.dw), A(op.dbias)
-                    for f in ("N", "C0", "C1", "Kpad", "B", "T", "Fin", "Fz", "No", "ostride", "ophase", "istride"):
-                        setattr(d, f, int(getattr(op, f)))
-                    d.ntaps = len(op.dt)
-                    d.precision = int(op.precision)
-                    d.bf16_mask = int(op.bf16_mask)
-                    for j in range(_lib.MAX_TAPS):
-                        d.dt[j] = op.dt[j] if j < len(op.dt) else 0
-                        d.ioff[j] = op.ioff[j] if j < len(op.ioff) else 0
-                else:
-                    for j, r in enumerate(op.p):
-                        o.p[j] = A(r)
-                    for j, v in enumerate(op.i):
-                        o.i[j] = C.c_int32(int(v) & 0xFFFFFFFF).value if v > 0x7FFFFFFF else int(v)
-                    for j, v in enumerate(op.f):
-                        o.f[j] = float(v)
-        self._bound = (in_ptr, out_ptr, dout_ptr, in2_ptr)
-
-    def _plan(self, which: str) -> list:
-        from .model import graph_branches_allowed
-        n = len(self.prog.fwd if which == "fwd" else self.prog.bwd)
-        sync = self.prog.sync.get(which) if (self.parallel_branches and graph_branches_allowed()) else None
-        return plan_segments(n, self.prog.lanes[which], sync) if sync else single_lane(n)
-
-    def _launch(self, which: str, stream: int, first: int, n: int) -> None:
-        arr = self.fwd if which == "fwd" else self.bwd
-        ops = C.cast(C.byref(arr, first * C.sizeof(_lib.Op)), C.POINTER(_lib.Op))
-        _lib.check(_lib.load().eab_run_program(ops, n, C.c_void_p(stream)), f"eab_run_program({which})")
-
-    def run(self, which: str, stream: int, first: int = 0, count: Optional[int] = None) -> None:
-        """Direct launches of ops [first, first + count) of one program.  Whole programs with parallel branches (the
-        post-filter's three S-TCM chains) fork onto side streams with events, exactly as their captured form replays."""
-        arr = self.fwd if which == "fwd" else self.bwd
-        if first == 0 and count is None:
-            plan = self._plan(which)
-            if len(plan) > 1:
-                assert torch.cuda.current_stream().cuda_stream == stream, "multi-lane programs run on torch's current stream"
-                if which not in self._direct:
-                    self._direct[which] = LaneGraphs(self.device, plan, lambda st, f, c, w=which: self._launch(w, st, f, c))
-                self._direct[which].run_direct()
-                return
-        self._launch(which, stream, first, len(arr) - first if count is None else count)
 
     def update_bn_buffers(self, module, momentum: float = 0.1) -> None:
         """nn.BatchNorm's train-mode side effect (NormSwitch BN branch, EaBNet.py:677-681): running_mean / running_var move
@@ -1208,11 +1086,12 @@ class TrainBound:
                                               C.c_void_p(stream)), "eab_gather_f32(grads)")
 
 
-class _EaBNetTrainFn(torch.autograd.Function):
-    """One autograd node for the whole network: forward program, backward program."""
+class TrainFn(torch.autograd.Function):
+    """One autograd node for a whole network: forward program, backward program.  ``inputs``: (x,) for EaBNet, (inpt, pre_x)
+    for GaGNet; no gradient flows to them.  ``sync_group``: see finish_flat_gradient."""
 
     @staticmethod
-    def forward(ctx, bound: TrainBound, sync_group, x: torch.Tensor, *params: torch.Tensor) -> torch.Tensor:
+    def forward(ctx, bound: TrainBound, sync_group, inputs: tuple, *params: torch.Tensor) -> torch.Tensor:
         prog = bound.prog
         ctx.sync_group = sync_group
         st = torch.cuda.current_stream().cuda_stream
@@ -1222,17 +1101,21 @@ class _EaBNetTrainFn(torch.autograd.Function):
         bound.pack(flat, st)
         bound.serial += 1
         ctx.serial = bound.serial
-        if bound.capture(tuple(x.shape)):
-            bound.static_x.copy_(x)
-            bound.graphs[0].replay()
-            out = bound.static_out.clone()
-            ctx.bound, ctx.x, ctx.dout, ctx.out = bound, None, None, None
+        x, x2 = inputs[0], (inputs[1] if len(inputs) > 1 else None)
+        out_shape = prog.out_shape or (prog.B, 2, prog.T, prog.F)
+        if bound.use_graph and bound.capture(tuple(x.shape), out_shape, out_shape, None if x2 is None else tuple(x2.shape)):
+            bound.static["in"].copy_(x)
+            if x2 is not None:
+                bound.static["in2"].copy_(x2)
+            bound.graphs["fwd"].replay()
+            out = bound.static["out"].clone()
+            ctx.io = None
         else:
-            out = torch.empty((prog.B, 2, prog.T, prog.F), dtype=torch.float32, device=x.device)
-            dout = torch.empty_like(out)
-            bound.bind(x.data_ptr(), out.data_ptr(), dout.data_ptr())
+            out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
+            ctx.io = (x, out, torch.empty_like(out), x2)
+            bound.bind(*(None if t is None else t.data_ptr() for t in ctx.io))
             bound.run("fwd", st)
-            ctx.bound, ctx.x, ctx.dout, ctx.out = bound, x, dout, out
+        ctx.bound = bound
         ctx.shapes = [p.shape for p in params]
         ctx.dtypes = [p.dtype for p in params]
         return out
@@ -1245,12 +1128,12 @@ class _EaBNetTrainFn(torch.autograd.Function):
             raise RuntimeError("eabnet_amd: backward of a forward pass whose saved activations were overwritten by a later "
                                "forward of the same module (one training program holds one set of activations)")
         bound.g.zero_()
-        if ctx.x is None:
-            bound.static_dout.copy_(grad_out)
-            bound.graphs[1].replay()
+        if ctx.io is None:
+            bound.static["dout"].copy_(grad_out)
+            bound.graphs["bwd"].replay()
         else:
-            ctx.dout.copy_(grad_out.to(torch.float32))
-            bound.bind(ctx.x.data_ptr(), ctx.out.data_ptr(), ctx.dout.data_ptr())
+            ctx.io[2].copy_(grad_out.to(torch.float32))
+            bound.bind(*(None if t is None else t.data_ptr() for t in ctx.io))
             bound.run("bwd", st)
         gflat = torch.empty(prog.n_params, dtype=torch.float32, device=bound.device)     # fresh per call: .grad may keep views of it
         bound.unpack_grads(gflat, st)
@@ -1277,12 +1160,13 @@ def finish_flat_gradient(gflat: torch.Tensor, sync_group, shapes, dtypes, needs)
     return grads
 
 
-def forward_train(module, inpt: torch.Tensor) -> torch.Tensor:
-    """EaBNet.forward under autograd on the HIP training programs.  The gradient w.r.t. the input spectrogram is not
-    produced (the reference's training never needs it)."""
+def forward_train(module, inputs: tuple, lower) -> torch.Tensor:
+    """A differentiable forward of ``module`` on its HIP training programs, lowered by ``lower(cfg, B, T, F, precision)``
+    (lower_train here, train_gag.lower_train for GaGNet).  ``inputs``: fp32, contiguous, (B, T, F, M, 2) for EaBNet or two
+    (B, 2, T, F) for GaGNet.  Returns the program's output arena ((B, 2, T, F), or (q, B, 2, T, F) for GaGNet)."""
     _lib.load()
-    B, T, F, M, _ = inpt.shape
-    x = inpt.detach().to(torch.float32).contiguous()
+    x = inputs[0]
+    B, T, F = (x.shape[0], x.shape[1], x.shape[2]) if x.ndim == 5 else (x.shape[0], x.shape[2], x.shape[3])
     cache = module.__dict__.setdefault("_train_bound", {})
     prec = "bf16" if module.precision == "bf16" else "f32"
     key = (B, T, F, str(x.device), prec)
@@ -1294,16 +1178,16 @@ def forward_train(module, inpt: torch.Tensor) -> torch.Tensor:
             torch.cuda.synchronize(x.device)      # the dropped program's arenas may still be read by kernels in flight
             cache.pop(next(iter(cache)))
         with torch.cuda.device(x.device):
-            bound = TrainBound(lower_train(module.cfg, B, T, F, prec), x.device)
+            bound = TrainBound(lower(module.cfg, B, T, F, prec), x.device)
     cache[key] = bound                               # most recently used last
     bound.use_graph = bool(getattr(module, "use_graph", True)) and not torch.cuda.is_current_stream_capturing()
     sd = dict(module.named_parameters())
     params = [sd[k] for k in bound.prog.keys]
     sync = module.__dict__.get("grad_allreduce", None)          # None | True (default group) | a process group
     with torch.cuda.device(x.device):
-        out = _EaBNetTrainFn.apply(bound, sync, x, *params)
+        out = TrainFn.apply(bound, sync, inputs, *params)
         bound.update_bn_buffers(module)
-    return out.to(inpt.dtype)
+    return out
 
 
 def enable_flat_allreduce(module, group=True) -> None:

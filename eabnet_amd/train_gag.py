@@ -17,17 +17,15 @@ gradient Slots, index images for parameter packing, deferred + batched weight gr
 channel count must be a multiple of 64."""
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Tuple
+from typing import Callable, Tuple
 
 import numpy as np
-import torch
 
-from . import _lib
 from . import program as prg
 from . import train as tr
 from .program import Ref, glu_row_order
 from .spec import GagConfig, gag_param_specs
-from .train import GenOp, TVar, TrainBound, TrainLowering, TrainProgram, _split64
+from .train import GenOp, TVar, TrainLowering, TrainProgram, _split64
 
 OP_GAG_PACK, OP_GAG_CRM, OP_GAG_CRM_BWD = prg.OP_GAG_PACK, prg.OP_GAG_CRM, 36
 PRE_LD = 384            # floats per (b, t) row of the interleaved previous estimate: 2*161 padded to a multiple of 64
@@ -196,86 +194,3 @@ class GagTrainLowering(TrainLowering):
 
 def lower_train(cfg: GagConfig, B: int, T: int, F: int = 161, precision: str = "f32") -> TrainProgram:
     return GagTrainLowering(cfg, B, T, F, precision).build()
-
-
-class _GagTrainFn(torch.autograd.Function):
-    """One autograd node for the whole post-filter: forward program, backward program."""
-
-    @staticmethod
-    def forward(ctx, bound: TrainBound, inpt: torch.Tensor, pre_x: torch.Tensor, *params: torch.Tensor) -> torch.Tensor:
-        prog = bound.prog
-        st = torch.cuda.current_stream().cuda_stream
-        flat = torch.cat([p.detach().reshape(-1) for p in params])      # (one batched copy; fp32 parameters)
-        if flat.dtype != torch.float32:
-            flat = flat.to(torch.float32)
-        bound.pack(flat, st)
-        bound.serial += 1
-        ctx.serial = bound.serial
-        if bound.capture(tuple(inpt.shape)):
-            bound.static_x.copy_(inpt)
-            bound.static_x2.copy_(pre_x)
-            bound.graphs[0].replay()
-            out = bound.static_out.clone()
-            ctx.io = None
-        else:
-            out = torch.empty(prog.out_shape, dtype=torch.float32, device=inpt.device)
-            dout = torch.empty_like(out)
-            bound.bind(inpt.data_ptr(), out.data_ptr(), dout.data_ptr(), pre_x.data_ptr())
-            bound.run("fwd", st)
-            ctx.io = (inpt, pre_x, out, dout)
-        ctx.bound = bound
-        ctx.shapes = [p.shape for p in params]
-        ctx.dtypes = [p.dtype for p in params]
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out: torch.Tensor):
-        bound, prog = ctx.bound, ctx.bound.prog
-        st = torch.cuda.current_stream().cuda_stream
-        if ctx.serial != bound.serial:
-            raise RuntimeError("eabnet_amd: backward of a forward pass whose saved activations were overwritten by a later "
-                               "forward of the same module (one training program holds one set of activations)")
-        bound.g.zero_()
-        if ctx.io is None:
-            bound.static_dout.copy_(grad_out)
-            bound.graphs[1].replay()
-        else:
-            inpt, pre_x, out, dout = ctx.io
-            dout.copy_(grad_out.to(torch.float32))
-            bound.bind(inpt.data_ptr(), out.data_ptr(), dout.data_ptr(), pre_x.data_ptr())
-            bound.run("bwd", st)
-        gflat = torch.empty(prog.n_params, dtype=torch.float32, device=bound.device)
-        bound.unpack_grads(gflat, st)
-        grads = tr.finish_flat_gradient(gflat, getattr(ctx.bound, "sync_group", None), ctx.shapes, ctx.dtypes, ctx.needs_input_grad[3:])
-        return (None, None, None, *grads)
-
-
-def forward_train(module, inpt: torch.Tensor, pre_x: torch.Tensor) -> List[torch.Tensor]:
-    """GaGNet.forward under autograd on the HIP training programs: list of q estimates (B, 2, F, T) (views of one
-    (q, B, 2, T, F) tensor).  No gradient flows to inpt / pre_x (the reference detaches the beam-former's estimate)."""
-    _lib.load()
-    B, _, T, F = inpt.shape
-    a = inpt.detach().to(torch.float32).contiguous()
-    b = pre_x.detach().to(torch.float32).contiguous()
-    cache = module.__dict__.setdefault("_train_bound", {})
-    prec = "bf16" if module.precision == "bf16" else "f32"
-    key = (B, T, F, str(a.device), prec)
-    bound = cache.pop(key, None)
-    if bound is None:
-        # a small LRU of bound programs (variable-length batches, a smaller last batch, alternating train / validation
-        # shapes): re-lowering and re-capturing two hipGraphs on every shape change costs seconds
-        while len(cache) >= tr.TRAIN_BOUND_CACHE:
-            torch.cuda.synchronize(a.device)      # the dropped program's arenas may still be read by kernels in flight
-            cache.pop(next(iter(cache)))
-        with torch.cuda.device(a.device):
-            bound = TrainBound(lower_train(module.cfg, B, T, F, prec), a.device)
-    cache[key] = bound                               # most recently used last
-    bound.use_graph = bool(getattr(module, "use_graph", True)) and not torch.cuda.is_current_stream_capturing()
-    bound.sync_group = module.__dict__.get("grad_allreduce", None)
-    sd = dict(module.named_parameters())
-    params = [sd[k] for k in bound.prog.keys]
-    with torch.cuda.device(a.device):
-        out = _GagTrainFn.apply(bound, a, b, *params)
-        bound.update_bn_buffers(module)
-    out = out.to(inpt.dtype)
-    return [out[j].permute(0, 1, 3, 2) for j in range(out.shape[0])]

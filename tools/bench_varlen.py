@@ -63,9 +63,8 @@ def fresh(net):
     """drop every resident program (exact-shape slot and buckets) so that each pass starts cold"""
     for m in net.modules():
         if isinstance(m, eabnet_amd.model._HipModule):
-            m._bound, m._packed_version = {}, {}
-            m._varlen_bound.clear()
-            m._varlen_version.clear()
+            for cache in (m._bound, m._packed_version, m._varlen_bound, m._varlen_version):
+                cache.clear()
     import gc
     gc.collect()
     torch.cuda.synchronize()
