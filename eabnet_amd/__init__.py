@@ -11,8 +11,10 @@ from .spec import GagConfig, NetConfig, gag_param_specs, param_specs  # noqa: F4
 from .model import (EaBNet, GaGNet, EaBNetWithPostNet, make_gag_net, make_eabnet_with_postnet,  # noqa: F401
                     StreamingEnhancer, Pipeline, prepare_data, stft_compress, istft, filter_and_sum, numParams, com_mag_mse_loss,
                     stagewise_com_mag_mse_loss, eabnet_with_postnet_loss)
+from .enhance import Enhancer, plan_batches  # noqa: F401
 
-__all__ = ["EaBNet", "GaGNet", "EaBNetWithPostNet", "make_gag_net", "make_eabnet_with_postnet", "StreamingEnhancer", "Pipeline", "prepare_data",
+__all__ = ["EaBNet", "GaGNet", "EaBNetWithPostNet", "make_gag_net", "make_eabnet_with_postnet", "StreamingEnhancer", "Pipeline", "Enhancer", "plan_batches",
+           "prepare_data",
            "stft_compress", "istft", "filter_and_sum", "numParams", "com_mag_mse_loss", "stagewise_com_mag_mse_loss",
            "eabnet_with_postnet_loss",
            "NetConfig", "GagConfig", "param_specs", "gag_param_specs"]

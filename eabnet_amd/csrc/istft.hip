@@ -24,9 +24,14 @@
 #define ISTFT_THREADS 256
 #define ISTFT_MAX_NFFT 512
 
+// VARLEN (eab_istft_lens_f32): `lens` holds B frame counts; T is the capacity (row strides of spec and wav).  Utterance b is
+// inverted as by a launch with T = lens[b] -- frames t >= lens[b] are neither read nor added nor counted in the envelope --
+// and its samples from hop (lens[b] - 1) on are written as zeros.  The count is clamped to [1, T].
+template <bool VARLEN>
 __global__ __launch_bounds__(ISTFT_THREADS) void istft_kernel(const float* __restrict__ spec, const float* __restrict__ window,
                                                               const float* __restrict__ twiddle, float* __restrict__ wav,
-                                                              int T, int n_fft, int hop, int chunks, FftPlan plan) {
+                                                              int T, int n_fft, int hop, int chunks, FftPlan plan,
+                                                              const int* __restrict__ lens) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int NH = n_fft / 2, F = NH + 1;
     const int R = (n_fft + hop - 1) / hop;                        // most frames that cover one output sample (2 for the reference)
@@ -38,6 +43,17 @@ __global__ __launch_bounds__(ISTFT_THREADS) void istft_kernel(const float* __res
     const int tid = threadIdx.x;
     const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
     const int t0 = chunk * (FFT_SIGS - (R - 1));                  // consecutive workgroups share R-1 frames
+    const int Tb = VARLEN ? (lens[b] > T ? T : (lens[b] < 1 ? 1 : lens[b])) : T;   // frames of this utterance
+    if (VARLEN && t0 >= Tb) {
+        // every frame of this workgroup lies past the utterance (workgroup-uniform, before any barrier): its positions
+        // start at t0 hop + n_fft - hop - n_fft/2 >= hop (Tb - 1), all of them padding -- zeros, no transform
+        const int p0 = t0 * hop + n_fft - hop, p1 = p0 + (FFT_SIGS - (R - 1)) * hop, cap_len = hop * (T - 1);
+        for (int p = p0 + tid; p < p1; p += ISTFT_THREADS) {
+            const int j = p - NH;
+            if (j >= 0 && j < cap_len) wav[(size_t)b * cap_len + j] = 0.0f;
+        }
+        return;
+    }
 
     for (int k = tid; k < n_fft; k += ISTFT_THREADS) {
         const float2 cs = reinterpret_cast<const float2*>(twiddle)[k];     // (cos, sin)(+theta)
@@ -49,7 +65,7 @@ __global__ __launch_bounds__(ISTFT_THREADS) void istft_kernel(const float* __res
         const int c = e / (2 * F), r = e - c * 2 * F;
         const int ri = r / F, f = r - ri * F;
         const int t = t0 + c;
-        xs[e] = t < T ? spec[(((size_t)b * 2 + ri) * T + t) * F + f] : 0.0f;
+        xs[e] = t < Tb ? spec[(((size_t)b * 2 + ri) * T + t) * F + f] : 0.0f;
     }
     __syncthreads();
     // conj(Z[k]),  Z = E + iO
@@ -76,18 +92,22 @@ __global__ __launch_bounds__(ISTFT_THREADS) void istft_kernel(const float* __res
     const int per = FFT_SIGS - (R - 1);
     const int p_lo = chunk == 0 ? 0 : t0 * hop + n_fft - hop;
     const int p_hi = (t0 + per) * hop + n_fft - hop;
-    const int out_len = hop * (T - 1);
+    const int out_len = hop * (T - 1), len_b = hop * (Tb - 1);     // row stride of wav; samples of this utterance
     for (int e = tid; e < p_hi - p_lo; e += ISTFT_THREADS) {
         const int p = p_lo + e;
         const int j = p - NH;                                      // output sample (centre trim of n_fft/2)
         if (j < 0 || j >= out_len) continue;
+        if (VARLEN && j >= len_b) {                                // past the utterance's trim: zero
+            wav[(size_t)b * out_len + j] = 0.0f;
+            continue;
+        }
         const int th = p / hop;
         float acc = 0.0f, env = 0.0f;
         for (int r = 0; r < R; ++r) {
             const int t = th - r;
             const int idx = p - t * hop;                           // sample of frame t; float index = idx (re/im interleave)
             if (t < 0 || idx >= n_fft) break;
-            if (t >= T) continue;
+            if (t >= Tb) continue;
             float a = yf[(t - t0) * n_fft + idx];
             if (idx & 1) a = -a;
             const float w = win[idx];
@@ -98,8 +118,9 @@ __global__ __launch_bounds__(ISTFT_THREADS) void istft_kernel(const float* __res
     }
 }
 
-extern "C" int eab_istft_f32(const float* spec, const float* window, const float* twiddle, float* wav, int B, int T,
-                             int n_fft, int hop, eab_stream_t stream) {
+// lens == NULL: every utterance is T frames long (eab_istft_f32); else per-utterance frame counts in a batch of capacity T
+static int istft_launch(const float* spec, const float* window, const float* twiddle, float* wav, const int* lens, int B, int T,
+                        int n_fft, int hop, eab_stream_t stream) {
     EAB_CHECK_ARG(spec && window && twiddle && wav);
     EAB_CHECK_ARG(B > 0 && T >= 2 && hop > 0);
     EAB_CHECK_ARG(n_fft >= 4 && n_fft <= ISTFT_MAX_NFFT && (n_fft % 2) == 0);
@@ -114,7 +135,21 @@ extern "C" int eab_istft_f32(const float* spec, const float* window, const float
     const int chunks = need <= 0 ? 1 : (int)((need + (long long)per * hop - 1) / ((long long)per * hop));
     EAB_CHECK_ARG((long long)B * chunks < (1ll << 31));
     const size_t sh = (size_t)(2 * n_fft + 2 * FFT_SIGS * n_fft + n_fft + FFT_SIGS * 2 * (n_fft / 2 + 1)) * sizeof(float);
-    hipLaunchKernelGGL(istft_kernel, dim3(B * chunks), dim3(ISTFT_THREADS), sh, eab_stream(stream), spec, window, twiddle,
-                       wav, T, n_fft, hop, chunks, plan);
+    if (lens)
+        hipLaunchKernelGGL(istft_kernel<true>, dim3(B * chunks), dim3(ISTFT_THREADS), sh, eab_stream(stream), spec, window, twiddle,
+                           wav, T, n_fft, hop, chunks, plan, lens);
+    else
+        hipLaunchKernelGGL(istft_kernel<false>, dim3(B * chunks), dim3(ISTFT_THREADS), sh, eab_stream(stream), spec, window, twiddle,
+                           wav, T, n_fft, hop, chunks, plan, lens);
     EAB_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int eab_istft_f32(const float* spec, const float* window, const float* twiddle, float* wav, int B, int T,
+                             int n_fft, int hop, eab_stream_t stream) {
+    return istft_launch(spec, window, twiddle, wav, nullptr, B, T, n_fft, hop, stream);
+}
+
+extern "C" int eab_istft_lens_f32(const float* spec, const float* window, const float* twiddle, float* wav, const int32_t* lens,
+                                  int B, int T_cap, int n_fft, int hop, eab_stream_t stream) {
+    return istft_launch(spec, window, twiddle, wav, lens, B, T_cap, n_fft, hop, stream);
 }

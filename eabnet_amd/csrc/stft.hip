@@ -30,15 +30,42 @@ __device__ __forceinline__ int reflect_index(int i, int P, int L) {
     return j;
 }
 
+// Per-utterance sample counts (eab_stft_compress_lens_f32): utterance b is the first lens[b] samples of its rows, which stay
+// L (the capacity) apart.  The count is clamped to (n_fft/2, L], so the gather stays in bounds whatever the array holds.
+__device__ __forceinline__ int stft_utt_len(const int* __restrict__ lens, int b, int n_fft, int L) {
+    const int n = lens[b];
+    return n > L ? L : (n <= n_fft / 2 ? n_fft / 2 + 1 : n);
+}
+
+// A frame past its utterance's last one: the frame's output as zeros, nothing gathered or transformed.
+__device__ __forceinline__ void stft_zero_frame(float* __restrict__ out, int b, int t, int T, int F, int M, int layout, int tid) {
+    if (layout == EAB_STFT_LAYOUT_BTFM2) {
+        float2* o = reinterpret_cast<float2*>(out) + ((size_t)b * T + t) * F * M;
+        for (int e = tid; e < F * M; e += STFT_THREADS) o[e] = make_float2(0.0f, 0.0f);
+    } else {                                                // (B,2,T,F), M == 1
+        for (int e = tid; e < 2 * F; e += STFT_THREADS) {
+            const int ri = e >= F;
+            out[(((size_t)b * 2 + ri) * T + t) * F + (e - ri * F)] = 0.0f;
+        }
+    }
+}
+
+// VARLEN: `lens` holds B sample counts, L is the row stride (capacity) and T = 1 + L / hop the frames per utterance of `out`.
+template <bool VARLEN>
 __global__ __launch_bounds__(STFT_THREADS) void stft_dft_kernel(
     const float* __restrict__ wav, const float* __restrict__ window, const float* __restrict__ twiddle,
-    float* __restrict__ out, int M, int L, int n_fft, int hop, int T, int layout) {
+    float* __restrict__ out, int M, int L, int n_fft, int hop, int T, int layout, const int* __restrict__ lens) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float2* tw = reinterpret_cast<float2*>(smem);           // [n_fft] (cos, sin)
     float* fr = smem + 2 * n_fft;                           // [n_fft][STFT_MC]
     const int F = n_fft / 2 + 1;
     const int b = blockIdx.x / T, t = blockIdx.x % T;
     const int tid = threadIdx.x;
+    const int Lb = VARLEN ? stft_utt_len(lens, b, n_fft, L) : L;   // samples of this utterance (reflection, last frame)
+    if (VARLEN && t > Lb / hop) {                           // workgroup-uniform: before any barrier
+        stft_zero_frame(out, b, t, T, F, M, layout, tid);
+        return;
+    }
 
     for (int k = tid; k < n_fft; k += STFT_THREADS) tw[k] = reinterpret_cast<const float2*>(twiddle)[k];
 
@@ -49,7 +76,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_dft_kernel(
             int mm = e / n_fft, n = e - mm * n_fft;        // consecutive threads -> consecutive samples
             float v = 0.0f;
             if (m0 + mm < M) {
-                int j = reflect_index(t * hop + n, n_fft / 2, L);
+                int j = reflect_index(t * hop + n, n_fft / 2, Lb);
                 v = window[n] * wav[((size_t)b * M + m0 + mm) * L + j];
             }
             fr[n * STFT_MC + mm] = v;
@@ -99,10 +126,13 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_dft_kernel(
 // interior frames, reflected scalar loads otherwise) with the window factor left out, and the gathered LDS rows stored
 // instead of transformed: frames[b][m][t][n] must equal reflect_pad(wav[b][m], n_fft/2)[t*hop + n] bit for bit
 // (train_distributed.py:83, torch.stft(center=True, pad_mode="reflect")).
-template <int NFFT_CT, int HOP_CT, bool DUMP>
+// VARLEN: as for stft_dft_kernel -- per-utterance sample counts `lens`, rows L apart, T frames per utterance of `out`; the
+// frames of an utterance are gathered, reflected and transformed exactly as by a launch with L = lens[b].
+template <int NFFT_CT, int HOP_CT, bool DUMP, bool VARLEN = false>
 __global__ __launch_bounds__(STFT_THREADS) void stft_fft_kernel(
     const float* __restrict__ wav, const float* __restrict__ window, const float* __restrict__ twiddle,
-    float* __restrict__ out, int M, int L, int n_fft_rt, int hop_rt, int T, int layout, FftPlan plan) {
+    float* __restrict__ out, int M, int L, int n_fft_rt, int hop_rt, int T, int layout, FftPlan plan,
+    const int* __restrict__ lens = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int n_fft = NFFT_CT ? NFFT_CT : n_fft_rt, hop = HOP_CT ? HOP_CT : hop_rt;
     const int NH = n_fft / 2, F = NH + 1;
@@ -129,6 +159,11 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_fft_kernel(
     }
     const int t = (int)vblk - b * T;
     const int tid = threadIdx.x;
+    const int Lb = VARLEN ? stft_utt_len(lens, b, n_fft, L) : L;          // samples of this utterance (reflection, last frame)
+    if (VARLEN && t > Lb / hop) {                                         // workgroup-uniform: before any barrier
+        stft_zero_frame(out, b, t, T, F, M, layout, tid);
+        return;
+    }
     if (!DUMP)
         for (int k = tid; k < n_fft; k += STFT_THREADS) {   // table is (cos, sin)(+theta); the passes use exp(-i theta)
             const float2 cs = reinterpret_cast<const float2*>(twiddle)[k];
@@ -139,7 +174,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_fft_kernel(
         __syncthreads();
         // gather + window: z_mm[n/2].(re|im) = w[n] x_mm[reflect(t hop + n)]; consecutive threads -> consecutive samples
         const int first = t * hop - NH;                                   // first sample of the frame (reflect padding: may be < 0)
-        if (first >= 0 && first + n_fft <= L && ((first | L | n_fft) & 3) == 0) {
+        if (first >= 0 && first + n_fft <= Lb && ((first | L | n_fft) & 3) == 0) {   // (alignment: the row stride L)
             // interior frame (all but the first and last of an utterance): no reflection, four samples per load
             // 32 threads per microphone walk its n_fft / 4 four-sample groups (no index division)
             const int n4 = n_fft >> 2, mm = tid >> 5;
@@ -162,7 +197,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_fft_kernel(
                 const int mm = e / n_fft, n = e - mm * n_fft;
                 float v = 0.0f;
                 if (m0 + mm < M) {
-                    const float x = wav[((size_t)b * M + m0 + mm) * L + reflect_index(t * hop + n, NH, L)];
+                    const float x = wav[((size_t)b * M + m0 + mm) * L + reflect_index(t * hop + n, NH, Lb)];
                     v = DUMP ? x : window[n] * x;
                 }
                 reinterpret_cast<float*>(buf0)[mm * n_fft + n] = v;       // float index 2*(n/2) + (n&1) = n
@@ -227,8 +262,10 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_fft_kernel(
     }
 }
 
-extern "C" int eab_stft_compress_f32(const float* wav, const float* window, const float* twiddle, float* out,
-                                     int B, int M, int L, int n_fft, int hop, int layout, eab_stream_t stream) {
+// lens == NULL: every utterance is L samples long (eab_stft_compress_f32); else per-utterance sample counts, rows L apart
+template <bool VARLEN>
+static int stft_compress_launch(const float* wav, const float* window, const float* twiddle, float* out, const int* lens,
+                                int B, int M, int L, int n_fft, int hop, int layout, eab_stream_t stream) {
     EAB_CHECK_ARG(wav && window && twiddle && out);
     EAB_CHECK_ARG(B > 0 && M > 0 && hop > 0);
     EAB_CHECK_ARG(n_fft >= 2 && n_fft <= STFT_MAX_NFFT && (n_fft % 2) == 0);
@@ -242,17 +279,29 @@ extern "C" int eab_stft_compress_f32(const float* wav, const float* window, cons
         // the reference front end (fft 320, hop 160) has its own instance: every size a constant, its passes written out
         // (independent of what fft_plan picks for the generic kernel)
         if (n_fft == 320 && hop == 160)
-            hipLaunchKernelGGL((stft_fft_kernel<320, 160, false>), dim3(B * T), dim3(STFT_THREADS), sh, eab_stream(stream), wav, window,
-                               twiddle, out, M, L, n_fft, hop, T, layout, plan);
+            hipLaunchKernelGGL((stft_fft_kernel<320, 160, false, VARLEN>), dim3(B * T), dim3(STFT_THREADS), sh, eab_stream(stream), wav,
+                               window, twiddle, out, M, L, n_fft, hop, T, layout, plan, lens);
         else
-            hipLaunchKernelGGL((stft_fft_kernel<0, 0, false>), dim3(B * T), dim3(STFT_THREADS), sh, eab_stream(stream), wav, window,
-                               twiddle, out, M, L, n_fft, hop, T, layout, plan);
+            hipLaunchKernelGGL((stft_fft_kernel<0, 0, false, VARLEN>), dim3(B * T), dim3(STFT_THREADS), sh, eab_stream(stream), wav,
+                               window, twiddle, out, M, L, n_fft, hop, T, layout, plan, lens);
         EAB_RETURN_LAUNCH_STATUS();
     }
     size_t shmem = (size_t)(2 * n_fft + n_fft * STFT_MC) * sizeof(float);
-    hipLaunchKernelGGL(stft_dft_kernel, dim3(B * T), dim3(STFT_THREADS), shmem, eab_stream(stream), wav,
-                       window, twiddle, out, M, L, n_fft, hop, T, layout);
+    hipLaunchKernelGGL(stft_dft_kernel<VARLEN>, dim3(B * T), dim3(STFT_THREADS), shmem, eab_stream(stream), wav,
+                       window, twiddle, out, M, L, n_fft, hop, T, layout, lens);
     EAB_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int eab_stft_compress_f32(const float* wav, const float* window, const float* twiddle, float* out,
+                                     int B, int M, int L, int n_fft, int hop, int layout, eab_stream_t stream) {
+    return stft_compress_launch<false>(wav, window, twiddle, out, nullptr, B, M, L, n_fft, hop, layout, stream);
+}
+
+extern "C" int eab_stft_compress_lens_f32(const float* wav, const float* window, const float* twiddle, float* out,
+                                          const int32_t* lens, int B, int M, int L_cap, int n_fft, int hop, int layout,
+                                          eab_stream_t stream) {
+    if (!lens) return stft_compress_launch<false>(wav, window, twiddle, out, nullptr, B, M, L_cap, n_fft, hop, layout, stream);
+    return stft_compress_launch<true>(wav, window, twiddle, out, lens, B, M, L_cap, n_fft, hop, layout, stream);
 }
 
 extern "C" int eab_stft_frames_f32(const float* wav, float* frames, int B, int M, int L, int n_fft, int hop,

@@ -259,10 +259,11 @@ def bucket_for(T: int, caps) -> Optional[int]:
     return None
 
 
-def check_lengths(lengths, B: int, T: int):
-    """Validate a ``lengths=`` argument: a (B,) sequence or integer tensor with 1 <= len <= T.  Host values are checked and
+def check_lengths(lengths, B: int, T: int, lo: int = 1, unit: str = "the call's frame count", integral: bool = False):
+    """Validate a ``lengths=`` argument: a (B,) sequence or integer tensor with lo <= len <= T.  Host values are checked and
     returned as a list; a device tensor is checked for shape and dtype only (its values would need a host synchronisation)
-    and returned as is -- the kernels stay in bounds for any value."""
+    and returned as is -- the kernels stay in bounds for any value.  integral: also refuse sequence members that are not
+    whole numbers (the front and back end; the networks' forward converts them with int(), as it always has)."""
     if isinstance(lengths, torch.Tensor):
         if lengths.dtype.is_floating_point or lengths.dtype == torch.bool or lengths.is_complex():
             raise ValueError(f"lengths must be integers, got {lengths.dtype}")
@@ -272,13 +273,25 @@ def check_lengths(lengths, B: int, T: int):
             return lengths
         vals = [int(v) for v in lengths.tolist()]
     else:
-        vals = [int(v) for v in lengths]
+        vals = list(lengths)
+        if integral and any(isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v
+                            for v in vals):
+            raise ValueError(f"lengths must be integers, got {vals[:4]}")
+        vals = [int(v) for v in vals]
         if len(vals) != B:
             raise ValueError(f"lengths must hold {B} values (one per utterance), got {len(vals)}")
-    bad = [v for v in vals if not 1 <= v <= T]
+    bad = [v for v in vals if not lo <= v <= T]
     if bad:
-        raise ValueError(f"lengths must lie in [1, {T}] (the call's frame count), got {bad[:4]}")
+        raise ValueError(f"lengths must lie in [{lo}, {T}] ({unit}), got {bad[:4]}")
     return vals
+
+
+def _device_lengths(lens, device: torch.device) -> torch.Tensor:
+    """checked lengths (check_lengths) as an int32 device array, enqueued on the current stream without a host synchronisation:
+    a device tensor device-to-device, host values through a pinned copy"""
+    if isinstance(lens, torch.Tensor):
+        return lens.to(device=device, dtype=torch.int32, non_blocking=True).contiguous()
+    return torch.as_tensor(lens, dtype=torch.int32).pin_memory().to(device, non_blocking=True)
 
 
 def _refuse_differentiable(module: nn.Module, what: str, reason: str):
@@ -345,10 +358,11 @@ class _HipModule(nn.Module):
         return {k: sd[k].detach().to("cpu", torch.float32).numpy() for k, s in self._specs.items()
                 if s.kind != "bn_count"}
 
-    def _program(self, B: int, T: int, F: int, device: torch.device, varlen: bool = False) -> _Bound:
+    def _program(self, B: int, T: int, F: int, device: torch.device, varlen: bool = False, fit: bool = False) -> Optional[_Bound]:
         """The bound program of (B, T, F) on ``device``, its packed weights current.  Exact-shape programs keep one shape
         resident (activations can be GBs); length-bucketed (varlen) ones live in an LRU bounded by max_resident_programs
-        and max_resident_bytes."""
+        and max_resident_bytes.  fit: a new program whose arena alone exceeds the byte budget is not built (None; the
+        caches stay as they are) instead of being admitted alone."""
         chains = bool(self.__dict__.get("parallel_chains", True))
         key = (B, T, F, str(device), self.precision, chains)
         cache, versions = (self._varlen_bound, self._varlen_version) if varlen else (self._bound, self._packed_version)
@@ -361,6 +375,8 @@ class _HipModule(nn.Module):
                              parallel_chains=chains, varlen=varlen)
             if stale:
                 need = 4 * max(prog.act_floats, 1)
+                if fit and need > budget:
+                    return None
                 while cache and (len(cache) >= limit or sum(4 * b.acts.numel() for b in cache.values()) + need > budget):
                     old, _ = cache.popitem(last=False)            # least recently used
                     versions.pop(old, None)
@@ -1032,8 +1048,14 @@ def _twiddle(n_fft: int, device: torch.device) -> torch.Tensor:
     return _TWIDDLE[key]
 
 
-def stft_compress(wav: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, layout: int = 0) -> torch.Tensor:
-    """(B, M, L) -> (B, T, F, M, 2)  [layout 0]  or (B, 1, L) -> (B, 2, T, F)  [layout 1]."""
+def stft_compress(wav: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, layout: int = 0, lengths=None) -> torch.Tensor:
+    """(B, M, L) -> (B, T, F, M, 2)  [layout 0]  or (B, 1, L) -> (B, 2, T, F)  [layout 1].
+
+    lengths: optional (B,) sample counts, n_fft/2 < len <= L (a sequence or an integer tensor, host or device): utterance b
+    is wav[b, :, :len[b]] and the rest of its rows is padding.  Its 1 + len[b] // hop frames are those of a call on that
+    utterance alone, bit for bit (the last frames reflect about ITS last sample); the frames after them are zeros."""
+    if lengths is not None:
+        lengths = check_lengths(lengths, wav.shape[0], wav.shape[2], lo=n_fft // 2 + 1, unit="n_fft/2 < samples <= L", integral=True)
     if not wav.is_cuda:
         raise _lib.EabError("stft_compress needs a CUDA (ROCm) tensor; there is no CPU fallback by design.")
     lib = _lib.load()
@@ -1044,6 +1066,13 @@ def stft_compress(wav: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor,
     out = torch.empty((B, T, F, M, 2) if layout == 0 else (B, 2, T, F), dtype=torch.float32, device=wav.device)
     with torch.cuda.device(wav.device):
         tw = _twiddle(n_fft, wav.device)
+        if lengths is not None:
+            lens = _device_lengths(lengths, wav.device)
+            _lib.check(lib.eab_stft_compress_lens_f32(wav.data_ptr(), window.data_ptr(), tw.data_ptr(), out.data_ptr(),
+                                                      lens.data_ptr(), B, M, L, n_fft, hop, layout,
+                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                       "eab_stft_compress_lens_f32")
+            return out
         _lib.check(lib.eab_stft_compress_f32(wav.data_ptr(), window.data_ptr(), tw.data_ptr(), out.data_ptr(),
                                              B, M, L, n_fft, hop, layout,
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)),
@@ -1129,6 +1158,10 @@ class _HostStager:
         if slot["used"]:
             slot["copied"].synchronize()                 # the pinned buffer is free again (depth steps ago)
             self.stream.wait_event(slot["consumed"])     # the device buffer's readers were enqueued before this
+        else:
+            # first use of a slot: its device buffer is fresh from the caching allocator, which hands out blocks freed on the
+            # launch stream while kernels queued there may still write them -- the copy must not overtake those
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
         src = t
         if self.always_stage or not (t.is_pinned() and t.is_contiguous() and t.dtype == torch.float32):
             _host_copy(slot["pin"], t)                   # pageable / strided / other dtype: one host pass into pinned memory
@@ -1224,11 +1257,20 @@ def _check_nola(window: torch.Tensor, fft_num: int, hop: int, T: int) -> None:
                            f"window / hop: fft_num={fft_num}, win_shift={hop})")
 
 
-def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.Tensor) -> torch.Tensor:
+def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.Tensor, lengths=None) -> torch.Tensor:
     """The reference's back end (enhance.py:59-62, test.py:189-191, train_distributed.py:128-130)
     ``torch.istft(view_as_complex(esti.permute(0,3,2,1)), fft_num, win_shift, win_size, hann)`` in one
     HIP kernel: (B, 2, T, F) -> (B, win_shift*(T-1)).  Like the reference it inverts the estimate as
-    it is (compressed domain)."""
+    it is (compressed domain).
+
+    lengths: optional (B,) frame counts, 2 <= len <= T (a sequence or an integer tensor, host or device): utterance b is
+    esti_stft[b, :, :len[b]], later frames are never read.  Its first win_shift*(len[b]-1) samples are those of a call on
+    that utterance alone, bit for bit (the envelope counts its own frames only); the samples after them are zeros.  The
+    window-overlap condition is checked for the shortest and the longest host length (a device tensor: for T)."""
+    if lengths is not None:
+        if esti_stft.ndim != 4:
+            raise ValueError(f"expected (B,2,T,{fft_num // 2 + 1}), got {tuple(esti_stft.shape)}")
+        lengths = check_lengths(lengths, esti_stft.shape[0], esti_stft.shape[2], lo=2, integral=True)
     if not esti_stft.is_cuda:
         raise _lib.EabError("istft needs a CUDA (ROCm) tensor; there is no CPU fallback by design.")
     if esti_stft.ndim != 4 or esti_stft.shape[1] != 2 or esti_stft.shape[3] != fft_num // 2 + 1:
@@ -1245,11 +1287,18 @@ def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.T
                                   "(ceil(fft_num / win_shift) in 1..8; the reference's 320/160 is 2)")
     lib = _lib.load()
     B, _, T, _ = esti_stft.shape
-    _check_nola(window, fft_num, win_shift, T)
+    for n in ((T,) if lengths is None or isinstance(lengths, torch.Tensor) else sorted({min(lengths), max(lengths)})):
+        _check_nola(window, fft_num, win_shift, n)
     x = esti_stft.detach().to(torch.float32).contiguous()
     window = _device_window(window, x.device)
     wav = torch.empty((B, win_shift * (T - 1)), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
+        if lengths is not None:
+            lens = _device_lengths(lengths, x.device)
+            _lib.check(lib.eab_istft_lens_f32(x.data_ptr(), window.data_ptr(), _twiddle(fft_num, x.device).data_ptr(),
+                                              wav.data_ptr(), lens.data_ptr(), B, T, fft_num, win_shift,
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_istft_lens_f32")
+            return wav
         _lib.check(lib.eab_istft_f32(x.data_ptr(), window.data_ptr(), _twiddle(fft_num, x.device).data_ptr(),
                                      wav.data_ptr(), B, T, fft_num, win_shift,
                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_istft_f32")

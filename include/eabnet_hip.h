@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define EAB_ABI_VERSION 9
+#define EAB_ABI_VERSION 10
 
 #define EAB_OK          0
 #define EAB_EINVAL      1   /* bad argument (shape, alignment, limit) */
@@ -82,6 +82,18 @@ int eab_stft_compress_f32(const float* wav, const float* window, const float* tw
                           float* out, int B, int M, int L, int n_fft, int hop,
                           int layout, eab_stream_t stream);
 
+/* The same front end on a padded batch of utterances of different lengths.  `lens` points to DEVICE memory holding B sample
+ * counts, n_fft/2 < lens[b] <= L_cap (values outside are clamped into that range); NULL = eab_stft_compress_f32 with
+ * L = L_cap.
+ *   wav     [B][M][L_cap]    utterance b is the first lens[b] samples of its rows
+ *   out     as above with T = T_cap = 1 + L_cap/hop frames per utterance
+ * Utterance b has T_b = 1 + lens[b]/hop frames; frame t < T_b is reflect_pad(wav[b][m][:lens[b]], n_fft/2)[t*hop + k],
+ * windowed, transformed and compressed with the arithmetic of eab_stft_compress_f32 -- the same bits as a call on that
+ * utterance alone (the reflection is about ITS last sample, not the batch's).  Frames t >= T_b are written as zeros. */
+int eab_stft_compress_lens_f32(const float* wav, const float* window, const float* twiddle,
+                               float* out, const int32_t* lens, int B, int M, int L_cap, int n_fft,
+                               int hop, int layout, eab_stream_t stream);
+
 /* Verification twin of the framing step (the bit-exact contract for "STFT frame indexing",
  * train_distributed.py:83 torch.stft(center=True, pad_mode="reflect")): the product kernel of
  * eab_stft_compress_f32 itself, compiled to store the rows it gathered (un-windowed) instead of
@@ -106,6 +118,15 @@ int eab_stft_frames_f32(const float* wav, float* frames, int B, int M, int L, in
  * ------------------------------------------------------------------------ */
 int eab_istft_f32(const float* spec, const float* window, const float* twiddle, float* wav, int B, int T,
                   int n_fft, int hop, eab_stream_t stream);
+
+/* The same back end on a padded batch.  `lens` points to DEVICE memory holding B frame counts, 2 <= lens[b] <= T_cap
+ * (clamped to [1, T_cap]); NULL = eab_istft_f32 with T = T_cap.
+ *   spec    [B][2][T_cap][F]   utterance b is its first lens[b] frames; later frames are never read
+ *   wav     [B][hop*(T_cap-1)]
+ * The first hop*(lens[b]-1) samples of utterance b are those of a call on its lens[b] frames alone, bit for bit: the
+ * overlap-add and the window envelope take the frames t < lens[b] only.  The samples after them are written as zeros. */
+int eab_istft_lens_f32(const float* spec, const float* window, const float* twiddle, float* wav, const int32_t* lens,
+                       int B, int T_cap, int n_fft, int hop, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
  * GaGNet post-filter glue (reference GaGNet.py).  The convolutions of the post-filter
