@@ -71,6 +71,11 @@ class Op(C.Structure):
                 ("win", TimeWindow), ("conv", ConvDesc), ("wgrad", WgradDesc)]
 
 
+class ShiftDesc(C.Structure):
+    """mirror of eab_shift_desc: one tensor of a streaming program's carry table (eab_shift_rows_f32)"""
+    _fields_ = [("ptr", C.c_void_p), ("row_floats", C.c_int32), ("rows", C.c_int32)]
+
+
 class EabError(RuntimeError):
     pass
 
@@ -90,6 +95,7 @@ _SIGS = {
     "eab_bfw_filter_sum_win_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [TimeWindow, C.c_void_p]),
     "eab_mlp_bfw_filter_sum_f32": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 4 + [TimeWindow, C.c_void_p]),
     "eab_zero_rows_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [TimeWindow, C.c_void_p]),
+    "eab_shift_rows_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "eab_com_mag_mse_loss_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "eab_gag_pack_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [TimeWindow, C.c_void_p]),

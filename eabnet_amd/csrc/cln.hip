@@ -53,22 +53,26 @@ __global__ __launch_bounds__(CL_THREADS) void cln_frame_sums_kernel(const float*
     }
 }
 
-// per batch element: running sums over t -> (mean, rstd); state[b] = (sum, sum of squares) up to the last frame done
+// per batch element: running sums over t -> (mean, rstd); state = [B][2] (sum, sum of squares) up to the last frame done, then
+// [B] frames seen so far (a whole number in a double: the count of the statistics is P times it -- the row index + 1 from the
+// start of the utterance, and still the frames seen after a stream has moved its rows to the front of its window)
 __global__ __launch_bounds__(64) void cln_scan_kernel(const double* __restrict__ sums, int T, int P, float eps, const int* __restrict__ t_pos,
                                                       int t_count, double* __restrict__ state, float* __restrict__ mr) {
     if (threadIdx.x != 0) return;
     const int b = blockIdx.x;
     const int t_lo = t_pos ? *t_pos : 0;
     const int t_hi = t_pos ? (t_lo + t_count < T ? t_lo + t_count : T) : T;
-    double cs = 0.0, cq = 0.0;
+    double cs = 0.0, cq = 0.0, cn = 0.0;
     if (state && t_lo > 0) {
         cs = state[b * 2];
         cq = state[b * 2 + 1];
+        cn = state[2 * gridDim.x + b];
     }
     for (int t = t_lo; t < t_hi; ++t) {
         cs += sums[((size_t)b * T + t) * 2];
         cq += sums[((size_t)b * T + t) * 2 + 1];
-        const double cnt = (double)P * (double)(t + 1);
+        cn += 1.0;
+        const double cnt = (double)P * cn;
         const double mean = cs / cnt;
         double var = (cq - 2.0 * mean * cs) / cnt + mean * mean;        // the reference's expression (EaBNet.py:731, 764)
         *reinterpret_cast<float2*>(&mr[((size_t)b * T + t) * 2]) = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
@@ -76,6 +80,7 @@ __global__ __launch_bounds__(64) void cln_scan_kernel(const double* __restrict__
     if (state) {
         state[b * 2] = cs;
         state[b * 2 + 1] = cq;
+        state[2 * gridDim.x + b] = cn;
     }
 }
 
@@ -169,20 +174,23 @@ __global__ __launch_bounds__(CL_THREADS) void cln_step_kernel(const float* __res
     if (threadIdx.x == 0) {
         sums[((size_t)b * T + t) * 2] = s;
         sums[((size_t)b * T + t) * 2 + 1] = q;
-        double cs = 0.0, cq = 0.0;
+        double cs = 0.0, cq = 0.0, cn = 0.0;
         if (t > 0) {
             cs = state[b * 2];
             cq = state[b * 2 + 1];
+            cn = state[2 * gridDim.x + b];
         }
         cs += s;
         cq += q;
-        const double cnt = (double)P * (double)(t + 1);
+        cn += 1.0;
+        const double cnt = (double)P * cn;
         const double mean = cs / cnt;
         double var = (cq - 2.0 * mean * cs) / cnt + mean * mean;        // the reference's expression (EaBNet.py:731, 764)
         const float2 m = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
         *reinterpret_cast<float2*>(&mr[((size_t)b * T + t) * 2]) = m;
         state[b * 2] = cs;
         state[b * 2 + 1] = cq;
+        state[2 * gridDim.x + b] = cn;
         m_sh = m;
     }
     __syncthreads();

@@ -42,6 +42,35 @@ extern "C" int eab_zero_rows_f32(float* ptr, int B, int T, int row_floats, eab_t
     EAB_RETURN_LAUNCH_STATUS();
 }
 
+// Rebase of an endless stream (eabnet_amd/model.py, EaBNetStream): before the step that would pass the end of the resident
+// window, the rows later steps can still read -- descs[k].rows rows of tensor k, ending at the frame position src_pos -- move
+// to rows [H - rows, H) of the same [B][T][row_floats] tensor, and the stream goes on at position H.  One workgroup per
+// (tensor, utterance); src_pos >= 2 H keeps source and destination apart, so the move needs no ordering.  16-byte accesses
+// where the rows allow them (every workspace tensor; a network input of an odd microphone count has 8-byte rows and is
+// moved float by float).
+__global__ __launch_bounds__(256) void shift_rows_kernel(const eab_shift_desc* __restrict__ descs, int T, int src_pos, int H) {
+    const eab_shift_desc d = descs[blockIdx.x];
+    const int h = d.rows < H ? d.rows : H;                // (never more than H rows: a bad table stays inside the window)
+    if (h <= 0 || d.row_floats <= 0) return;
+    const size_t row = (size_t)d.row_floats, n = (size_t)h * row;
+    float* base = d.ptr + (size_t)blockIdx.y * T * row;
+    const float* src = base + (size_t)(src_pos - h) * row;
+    float* dst = base + (size_t)(H - h) * row;
+    if ((d.row_floats & 3) == 0 && ((uintptr_t)d.ptr & 15) == 0) {
+        for (size_t k = threadIdx.x; k < n / 4; k += blockDim.x)
+            reinterpret_cast<f32x4*>(dst)[k] = reinterpret_cast<const f32x4*>(src)[k];
+    } else {
+        for (size_t k = threadIdx.x; k < n; k += blockDim.x) dst[k] = src[k];
+    }
+}
+
+extern "C" int eab_shift_rows_f32(const eab_shift_desc* dev_descs, int n, int B, int T, int src_pos, int H, eab_stream_t stream) {
+    EAB_CHECK_ARG(dev_descs && n > 0 && B > 0 && B <= 65535 && T > 0 && H > 0);
+    EAB_CHECK_ARG(src_pos <= T && (long long)src_pos >= 2ll * H);       // rows [src_pos - H, src_pos) and [0, H): inside, disjoint
+    hipLaunchKernelGGL(shift_rows_kernel, dim3((unsigned)n, (unsigned)B), dim3(256), 0, eab_stream(stream), dev_descs, T, src_pos, H);
+    EAB_RETURN_LAUNCH_STATUS();
+}
+
 extern "C" int eab_abi_version(void) { return EAB_ABI_VERSION; }
 
 extern "C" const char* eab_error_string(int code) {

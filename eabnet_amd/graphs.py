@@ -111,12 +111,18 @@ def _pick(device: torch.device, n: int, fixed: List[torch.cuda.Stream], pool: Li
     with torch.cuda.device(device):
         ref = fixed[0] if fixed else torch.cuda.current_stream(device)
         _overlap(ref, torch.cuda.Stream(device=device), device)             # (first launch: module load)
-        alone = min(_overlap(ref, ref, device) for _ in range(2)) / 2.0      # one spin kernel
+        # The spin kernel counts clock cycles, so it runs long while the clocks are still low after an idle stretch (a program
+        # is lowered on the host just before its streams are picked).  A calibration taken then lets two kernels on ONE queue,
+        # timed a moment later at full clocks, pass for overlapping.  So: a few spins first, the shortest of several timings
+        # as the time of one kernel, and the shorter of two timings per pair (host jitter only ever adds).
+        for _ in range(8):
+            _overlap(ref, ref, device)
+        alone = min(_overlap(ref, ref, device) for _ in range(4)) / 2.0      # one spin kernel
         cands = [make() for _ in range(8)]
         for c in cands:
             if len(pool) >= n:
                 break
-            if all(_overlap(o, c, device) < 1.5 * alone for o in fixed + pool):
+            if all(min(_overlap(o, c, device) for _ in range(2)) < 1.5 * alone for o in fixed + pool):
                 pool.append(c)
         spare = [c for c in cands if c not in pool]
         pool += spare[:max(0, n - len(pool))]

@@ -96,6 +96,7 @@ class _Bound(BoundProgram):
         self.window = {"t_pos": self.t_pos.data_ptr() if prog.chunk else None, "chunk": prog.chunk,
                        "lens": self.lens.data_ptr() if prog.varlen else None}
         self.exec_ops, self.n_exec, self.chains = None, 0, []
+        self._carry_dev = None              # the carry table in device memory (eab_shift_desc[]), for the current binding
 
     def reset_counters(self) -> None:
         """arrival counters of the fused InstanceNorm finalisation: zero before the first run (the kernels re-arm them
@@ -130,7 +131,34 @@ class _Bound(BoundProgram):
         if not super().bind(in_ptr, out_ptr, in2_ptr):
             return False
         self._plan_chains()
+        self._carry_dev = None
         return True
+
+    def upload_carry(self) -> None:
+        """The carry table of a streaming program (prog.carry) as eab_shift_desc[] in device memory, for the boundary
+        buffers the program is bound to: uploaded once per binding, like the descriptors of a chain launch."""
+        if self._carry_dev is not None or not self.prog.carry:
+            return
+        assert self._ptrs is not None, "bind the program first"
+        bases = {k: t.data_ptr() for k, t in self.arenas.items()}
+        bases.update(zip(self.BOUNDARY, self._ptrs))
+        descs = (_lib.ShiftDesc * len(self.prog.carry))()
+        for d, (ref, row, rows) in zip(descs, self.prog.carry):
+            d.ptr, d.row_floats, d.rows = bases[ref.arena] + 4 * ref.off, row, rows
+        self._carry_dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
+
+    def rebase(self, src_pos: int, stream: int) -> int:
+        """Move the rows a streaming program can still read at frame position ``src_pos`` to the front of the resident
+        window (one launch on ``stream``, eab_shift_rows_f32) and return the position the stream continues at
+        (prog.history).  Not part of the step's graph: it runs between two replays, on the launch stream."""
+        p = self.prog
+        if not (p.chunk and 2 * p.history <= src_pos <= p.T):
+            raise ValueError(f"rebase at position {src_pos} of a window of {p.T} frames with history {p.history}")
+        self.upload_carry()
+        if p.carry:
+            _lib.check(_lib.load().eab_shift_rows_f32(self._carry_dev.data_ptr(), len(p.carry), p.B, p.T, src_pos, p.history,
+                                                      C.c_void_p(stream)), "eab_shift_rows_f32")
+        return p.history
 
     def buffers(self, use_graph: bool, in_shape, out_shape, in2_shape=None):
         """(in, out, in2), launch: boundary buffers the program is bound to and the call that runs it on them -- the
@@ -494,12 +522,14 @@ class _HipModule(nn.Module):
         return out
 
     # -- streaming ------------------------------------------------------------------
-    def stream_begin(self, B: int, T_max: int, chunk: int = 1, F: int = 161, device=None) -> EaBNetStream:
+    def stream_begin(self, B: int, T_max: int, chunk: int = 1, F: int = 161, device=None, endless: bool = False) -> EaBNetStream:
         """Frame-synchronous inference (BASELINE config 5): returns a stream object whose
         ``step`` takes ``chunk`` new frames and returns the matching output frames (see EaBNetStream.step).
         Needs a configuration in which the network really is causal -- ``norm_type="BN"`` in eval mode (running
         statistics) or ``norm_type="cLN"`` (cumulative statistics), and ``is_causal=True`` -- and raises
-        NotImplementedError otherwise."""
+        NotImplementedError otherwise.  ``T_max`` is the longest utterance the stream takes; with ``endless=True`` it is
+        the resident window of a stream that takes frames forever (at least ``2 * history + chunk`` frames, ValueError
+        otherwise; see EaBNetStream)."""
         if self.training:
             raise RuntimeError("stream_begin: call .eval() first (BatchNorm must use its running statistics)")
         _lib.load()
@@ -510,7 +540,11 @@ class _HipModule(nn.Module):
             raise ValueError("chunk and T_max must be positive")
         with torch.cuda.device(device):
             prog = prg.lower(self.cfg, self._numpy_params(), B, T_max, F, precision=self.precision, chunk=chunk)
-            return EaBNetStream(self, _Bound(prog, device), B, T_max, F, chunk)
+            if endless and T_max < prog.min_window:
+                raise ValueError(f"endless stream: a window of T_max={T_max} frames is too small, this network reads "
+                                 f"{prog.history} frames back and needs at least {prog.min_window} "
+                                 f"(2 * {prog.history} + chunk)")
+            return EaBNetStream(self, _Bound(prog, device), B, T_max, F, chunk, endless)
 
     def _needs_graph(self, *inputs) -> bool:
         needs = torch.is_grad_enabled() and (any(x.requires_grad for x in inputs)
@@ -582,11 +616,18 @@ class EaBNetStream:
     program restricted to those time rows (eab_time_window: every kernel reads the frame position from
     device memory) and returns the new output frames.  Results are bit-identical to one offline call
     on the concatenated input, because every kernel computes a row independently of the tile or launch
-    it falls into and the LSTM state is carried exactly."""
+    it falls into and the LSTM state is carried exactly.
 
-    def __init__(self, net, bound: _Bound, B: int, T_max: int, F: int, chunk: int):
+    ``endless=True``: ``T_max`` is a resident window, not a limit.  A causal program reads a bounded number of earlier rows
+    (``history``: 128 frames for the default S-TCN, Program.carry per tensor).  When the next step would pass the end of
+    the window, the rows later steps can still read move to its front in one launch (eab_shift_rows_f32) and the stream
+    goes on at row ``history``; no read then reaches below row 0, so "rows before 0 are causal padding" still means
+    "before the start of the stream".  The frames stay those of one offline call on everything pushed since ``reset``."""
+
+    def __init__(self, net, bound: _Bound, B: int, T_max: int, F: int, chunk: int, endless: bool = False):
         self.net, self.bound, self.B, self.T_max, self.F, self.chunk = net, bound, B, T_max, F, chunk
-        self.pos = 0
+        self.endless = endless
+        self.pos = 0                                  # row of the resident window the next frame goes to
         self._closed = False
         self.post = isinstance(net, GaGNet)           # post-filter: two planar inputs, q stage outputs
         if self.post:
@@ -594,6 +635,14 @@ class EaBNetStream:
         else:
             in_shape, out_shape, in2_shape = (B, T_max, F, net.M, 2), (B, 2, T_max, F), None
         (self._in, self._out, self._in2), self._launch = bound.buffers(net.use_graph, in_shape, out_shape, in2_shape)
+        if endless:
+            assert T_max >= bound.prog.min_window
+            bound.upload_carry()
+
+    @property
+    def history(self) -> int:
+        """frames back the farthest reader of the program looks (Program.history): what an endless stream keeps"""
+        return self.bound.prog.history
 
     def reset(self) -> None:
         """Start a new batch of utterances (no buffer needs clearing: position 0 ignores all state)."""
@@ -611,10 +660,13 @@ class EaBNetStream:
         want = (self.B, 2, n, self.F) if self.post else (self.B, n, self.F, self.net.M, 2)
         if tuple(x.shape) != want or not 0 < n <= self.chunk or (self.post and (pre_x is None or pre_x.shape != x.shape)):
             raise ValueError(f"expected {want} with n <= {self.chunk}, got {tuple(x.shape)}")
-        if self.pos + n > self.T_max:
+        if not self.endless and self.pos + n > self.T_max:
             raise ValueError(f"utterance longer than the T_max={self.T_max} given to stream_begin")
         if not x.is_cuda:
             raise _lib.EabError("stream.step needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+        if self.endless and self.pos + self.chunk > self.T_max:
+            with torch.cuda.device(x.device):         # on the launch stream, between two replays of the step's graph
+                self.pos = self.bound.rebase(self.pos, torch.cuda.current_stream().cuda_stream)
         lo, hi, end = self.pos, self.pos + n, self.pos + self.chunk
         with torch.cuda.device(x.device), torch.no_grad():
             for buf, src in ((self._in, x), (self._in2, pre_x)):
@@ -926,9 +978,11 @@ class EaBNetWithPostNet(nn.Module):
         for p in self.eabnet.parameters():
             p.requires_grad = False
 
-    def stream_begin(self, B: int, T_max: int, chunk: int = 1) -> "TwoStageStream":
-        """Frame-synchronous two-stage inference: both stages need BatchNorm norms and causal S-TCMs."""
-        return TwoStageStream(self, self.eabnet.stream_begin(B, T_max, chunk), self.postnet.stream_begin(B, T_max, chunk))
+    def stream_begin(self, B: int, T_max: int, chunk: int = 1, endless: bool = False) -> "TwoStageStream":
+        """Frame-synchronous two-stage inference: both stages need BatchNorm norms and causal S-TCMs.  endless: T_max is
+        the resident window of both stages, each of which moves its own rows when it reaches the end (EaBNetStream)."""
+        return TwoStageStream(self, self.eabnet.stream_begin(B, T_max, chunk, endless=endless),
+                              self.postnet.stream_begin(B, T_max, chunk, endless=endless))
 
 
 class TwoStageStream:
@@ -959,10 +1013,13 @@ class StreamingEnhancer:
     identically wherever its window starts), so the streamed wave is bit-identical to the offline
     wave -> prepare_data -> model -> istft chain."""
 
-    def __init__(self, model, B: int, seconds: float, chunk: int = 1, sr: int = 16000, fft_num: int = 320, hop: int = 160):
+    def __init__(self, model, B: int, seconds: float, chunk: int = 1, sr: int = 16000, fft_num: int = 320, hop: int = 160,
+                 endless: bool = False):
+        """seconds: the longest stream; with endless=True the resident window of a stream of any length (see
+        EaBNetStream: it must hold twice the network's history plus a chunk)."""
         self.model, self.B, self.chunk, self.fft, self.hop = model, B, chunk, fft_num, hop
         self.T_max = 1 + int(seconds * sr) // hop
-        self.stream = model.stream_begin(B, self.T_max, chunk)
+        self.stream = model.stream_begin(B, self.T_max, chunk, endless=endless)
         self.window = torch.hann_window(fft_num)
         self.reset()
 

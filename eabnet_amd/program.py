@@ -468,6 +468,45 @@ class Program:
     # > 0 / True: per-utterance lengths (eab_time_window.lens): utterance b is its first lens[b] frames, read by every windowed
     # op from one device array [B] the binding owns (lower(..., varlen=True); causal configurations only)
     varlen: bool = False
+    # streaming programs: what a stream of any length has to keep (carry_table): carry = [(ref, floats per time row, rows)]
+    # for every tensor some op reads at an earlier row, history = H, the farthest reach (a multiple of chunk, at least 1).
+    # An offline program carries nothing (empty table, history 0).
+    carry: List[Tuple[Ref, int, int]] = field(default_factory=list)
+    history: int = 0
+
+    @property
+    def min_window(self) -> int:
+        """Smallest resident window (T) an endless stream of this program can run in: the H carried rows at the front, the
+        chunk being computed, and the H rows of the next move behind them without overlap (model.EaBNetStream)."""
+        return 2 * self.history + self.chunk
+
+
+def carry_table(ops: Sequence, chunk: int) -> Tuple[List[Tuple[Ref, int, int]], int]:
+    """(carry, history) of a finished streaming op list.  A windowed op computes the rows of the current chunk; whatever it
+    reads of an EARLIER row must survive when a stream moves its resident rows (eab_shift_rows_f32).  Who reads earlier rows:
+      * a convolution with negative time taps (dt, and ph1_dt of a two-phase launch) reads both of its sources that far back
+        (k1 = (2, 3) gated convolutions: one frame; S-TCM dilated convolutions: (kd1 - 1) * dilation frames);
+      * the LSTM reads the hidden state of the previous row back from h_out (its cell state is position-free).
+    Everything else works on rows of the chunk only: the fused second 1x1 convolution (f2_*) reads the rows its own launch has
+    just produced, residuals (aux, dst_acc), norm / gate / pack / head ops and the cLN statistics (position-free running
+    sums) have no taps.  history = the farthest reach, rounded up to a multiple of chunk and at least 1."""
+    reach: Dict[Ref, List[int]] = {}
+
+    def need(ref: Optional[Ref], row: int, rows: int) -> None:
+        if ref is None or rows <= 0:
+            return
+        e = reach.setdefault(ref, [row, 0])
+        assert e[0] == row, f"{ref}: read with {row} and {e[0]} floats per time row"
+        e[1] = max(e[1], rows)
+    for op in ops:
+        if op.kind == OP_CONV:
+            back = max([0] + [-d for d in list(op.dt) + list(op.ph1_dt)])
+            need(op.src0, op.Fin * op.C0, back)
+            need(op.src1, op.Fin * op.C1, back)
+        elif op.kind == OP_LSTM64:
+            need(op.h_out, op.F * 64, 1)
+    far = max([1] + [e[1] for e in reach.values()])
+    return [(ref, e[0], e[1]) for ref, e in reach.items()], -(-far // chunk) * chunk
 
 
 class Lowering:
@@ -579,7 +618,7 @@ class Lowering:
         B, T = self.B, self.T
         Pn = F * C
         sums = self.alloc(B * T * 4)                                  # [B][T][2] doubles
-        state = self.alloc(B * 4) if self.chunk else None             # [B][2] doubles
+        state = self.alloc(B * 6) if self.chunk else None             # [B][2] doubles (running sums), then [B] doubles (frames seen)
         mr = self.alloc(B * T * 2)
         gain = self.W.add(f"{norm}.norm.gain#c", self.P[f"{norm}.norm.gain"].reshape(C))
         bias = self.W.add(f"{norm}.norm.bias#c", self.P[f"{norm}.norm.bias"].reshape(C))
@@ -1319,7 +1358,7 @@ def lower(cfg, params: Dict[str, np.ndarray], B: int, T: int, F: int = 161,
           dump_bfw: bool = False, precision: str = "f32", chunk: int = 0, parallel_chains: bool = True,
           varlen: bool = False) -> Program:
     """chunk > 0 lowers the streaming form: T is then the longest utterance the resident activations can
-    hold and every op advances `chunk` frames per replay.  parallel_chains (GaGNet): the glance / gaze S-TCM
+    hold (or the window of an endless stream, at least Program.min_window) and every op advances `chunk` frames per replay.  parallel_chains (GaGNet): the glance / gaze S-TCM
     chains of a stage as parallel graph branches (best latency of one batch) or back to back (best when
     several batches are in flight anyway, eabnet_amd.Pipeline).  varlen: a program for up to T frames per
     utterance whose ops read per-utterance lengths from device memory (eab_time_window.lens): frames past an
@@ -1338,4 +1377,6 @@ def lower(cfg, params: Dict[str, np.ndarray], B: int, T: int, F: int = 161,
     else:
         prog = Lowering(cfg, params, B, T, F, dump_bfw, precision, chunk).build()
     prog.varlen = bool(varlen)
+    if chunk:
+        prog.carry, prog.history = carry_table(prog.ops, chunk)
     return prog

@@ -485,6 +485,20 @@ int eab_conv_st_chain_plan(const eab_conv_desc* descs, int n, int* codes, int* l
 int eab_conv_st_chain_run(const eab_conv_desc* dev_descs, const int* dev_codes, int n, int B, int lds_bytes, int bf16,
                           eab_stream_t stream);
 
+/* Streams of any length: a streaming program keeps [B][T][..] per tensor resident, and a causal program reads only a bounded
+ * number of earlier rows.  Before the step that would pass row T, eab_shift_rows_f32 moves, for every tensor k of the table,
+ * its rows [src_pos - rows_k, src_pos) to [H - rows_k, H) (all utterances, one launch); the caller then continues at
+ * position H.  rows_k = how far back any op reads tensor k, H >= max rows_k.  Needs 2 H <= src_pos <= T (source and
+ * destination rows disjoint), else EAB_EINVAL.  dev_descs: the table in DEVICE memory (uploaded once per binding, like the
+ * descriptors of eab_conv_st_chain_run); rows_k > H is treated as H.  Position-free state (LSTM cell state, cLN running
+ * sums and frame count) stays where it is. */
+typedef struct eab_shift_desc {
+    float* ptr;            /* tensor [B][T][row_floats] */
+    int32_t row_floats;
+    int32_t rows;
+} eab_shift_desc;
+int eab_shift_rows_f32(const eab_shift_desc* dev_descs, int n, int B, int T, int src_pos, int H, eab_stream_t stream);
+
 /* Windowed twins of the non-conv ops (same semantics restricted to the rows of `win`; win.pos == NULL
  * = the whole utterance).  eab_lstm64_stream_f32 additionally carries the recurrent state: the hidden
  * state of row *pos-1 is read back from h_out, the cell state lives in c_state [B*F][64] (read when
@@ -662,7 +676,10 @@ int eab_wgrad_batch_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, ea
  * channel = index % C.
  *   eab_cln_stats_f32: mr[b][t] = (cum_mean, 1/sqrt(cum_var + eps)) over all channels, bins and frames <= t, of x or --
  *     slope != NULL -- of prelu(x, slope[c]) (S-TCM order).  sums: scratch [B][T][2] doubles; state: [B][2] doubles,
- *     the running sums carried between streaming chunks (required with a window, optional otherwise).
+ *     the running sums carried between streaming chunks, followed by [B] doubles, the frames seen so far (3 B doubles in all;
+ *     required with a window, optional otherwise).  The count of the statistics of a frame is P times the frames seen, not
+ *     P (t + 1) of its row t: the same number while a stream fills its window from row 0, and still right after
+ *     eab_shift_rows_f32 has moved the stream to the front of its window.  State restarts where *win.pos == 0.
  *   eab_cln_apply_f32: y = prelu(gain_c (x-mean) rstd + bias_c, slope_c) [+ add]   (mode EAB_XF_NORM_PRELU)
  *                      y = gain_c (prelu(x, slope_c) - mean) rstd + bias_c         (mode EAB_XF_PRELU_NORM)
  *   eab_gate_rows_f32: z = a * sigmoid(r) (S-TCM gate, EaBNet.py:575) on [B][T][row_floats]
@@ -684,7 +701,8 @@ int eab_gate_rows_f32(const float* a, const float* r, float* z, int B, int T, in
                       eab_stream_t stream);
 /* One frame of a streaming step (win.count == 1): eab_cln_stats_f32 followed by eab_cln_apply_f32 on the same x in ONE launch
  * (one workgroup per utterance: frame sums -> running sums and mr[b][t] -> normalised frame).  Bit-identical to the two calls
- * (same reduction tree, same expressions); stat_slope = the statistics' PReLU slope (EAB_XF_PRELU_NORM) or NULL. */
+ * (same reduction tree, same expressions); stat_slope = the statistics' PReLU slope (EAB_XF_PRELU_NORM) or NULL; state as
+ * in eab_cln_stats_f32 ([B][2] running sums, then [B] frames seen). */
 int eab_cln_step_f32(const float* x, const float* stat_slope, double* sums, double* state, float* mr, const float* gain,
                      const float* bias, const float* slope, const float* add, float* y, int B, int T, int P, int C, int mode,
                      float eps, eab_time_window win, eab_stream_t stream);
