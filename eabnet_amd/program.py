@@ -753,6 +753,12 @@ class Lowering:
             self.flops += 2 * self.B * self.T * No * N * len(dt) * (C0 + C1)
         return op
 
+    def can_fuse_finalize(self, ops: Sequence[ConvOp]) -> bool:
+        """EAB_FUSE_FIN=1 and every producing launch is of a form whose kernel carries the fused finalisation: the small-tile
+        kernel (csrc/conv_st.hip) and the phase-pair form (EAB_EPI_PHASE2) refuse fz_counter, so their norms keep the
+        eab_in_finalize_f32 launch"""
+        return self.fuse_fin and all(op.korder != KORDER_FRAG and op.epi != EPI_PHASE2 for op in ops)
+
     def fuse_finalize(self, ops: Sequence[ConvOp], C: int, norms: Sequence[str]) -> List[Ref]:
         """InstanceNorm finalisation inside the producing launches `ops` (all feeding the same statistics): the tile
         that arrives last per utterance merges the partials and writes the (scale, shift) tables -- no extra launch.
@@ -835,7 +841,7 @@ class Lowering:
         if cln:
             return self.cln_norm(name, dst, Fout, Cout, norm, f"{act}.weight", XF_NORM_PRELU, add)
         if xf is None:
-            if self.fuse_fin:
+            if self.can_fuse_finalize([op]):
                 xf, = self.fuse_finalize([op], Cout, [norm])
             else:
                 xf, = self.emit_finalize(name + ".in", stats, Cout, 1, tiles, self.T * Fout, [norm])
@@ -929,7 +935,7 @@ class Lowering:
         if cln:
             return self.cln_norm(name, dst, Fout, Cout, norm, f"{act}.weight", XF_NORM_PRELU, add)
         if xf is None:
-            if self.fuse_fin:
+            if self.can_fuse_finalize(phase_ops):
                 xf, = self.fuse_finalize(phase_ops, Cout, [norm])
             else:
                 xf, = self.emit_finalize(name + ".in", stats, Cout, 1, sum(tiles), self.T * Fout, [norm])
