@@ -1,0 +1,218 @@
+// Evaluation scores per utterance of a padded batch, on the device (reference test.py:126-153 cal_single_metrics ->
+// metrics.py:14-39 energy_ratios, metrics.py:71-75 si_sdr; train_distributed.py:98-156 evaluate -> com_mag_mse_loss per file).
+//
+// eab_energy_ratios_f32: with n = y - s (every signal zero from its own length up to the longest of the three) the six sums
+//     A = s^.s^   S = s.s   N = n.n   P = s^.s   Q = s^.n   R = s.n          (fp64 products of the fp32 samples, fp64 sums)
+// give, with a_s = P/S and a_n = Q/N,
+//     |s_target|^2        = a_s^2 S                      |e_noise|^2 = a_n^2 N
+//     |e_art|^2           = A + a_s^2 S + a_n^2 N - 2 a_s P - 2 a_n Q + 2 a_s a_n R
+//     |e_noise + e_art|^2 = A - P^2/S                    (s^ minus its projection on s)
+//     si_sdr(s, y)        = 10 log10( ((S+R)^2/S) / (N - R^2/S) )            (y = s + n)
+// from ONE read of each signal.  The closed forms lose digits only where |e_art|^2 is ~1e-10 of A (SAR ~ 100 dB).
+//
+// eab_com_mag_mse_loss_lens_f32: the masked loss of loss.hip for every utterance alone; its valid bins are the first
+// frames[b]*F floats of each of its two planes, i.e. two contiguous rows per spectrum.
+//
+// Determinism (both): the sample (bin) index is cut into SPANS of SCORE_SPAN = 4096, workgroup (span, b) owns span `span` of
+// utterance b whatever B, the row length, the row's alignment and the neighbours are.  Inside a span lane `tid` owns the indices
+// j*1024 + 4*tid + {0..3}, j = 0..3, and adds them in that order; a row whose address is 16-byte aligned loads its four as one
+// dwordx4, any other row (and the quad that straddles the row's length) loads them one by one AT THE SAME indices, so the bits do
+// not depend on the load path.  Lanes are added by a fixed shuffle tree, the four waves in wave order through LDS, the spans in
+// index order by the final kernel.  No atomics.  Samples at or past a signal's length are never read.
+// Bound: launch latency and HBM (3 * L * 4 bytes per utterance; 4 * frames * F * 4 bytes for the loss).
+#include "common.h"
+
+#define SCORE_THREADS 256
+#define SCORE_SPAN 4096                       /* samples per workgroup: 4 rounds of 256 lanes x 4 samples */
+#define SCORE_MAX_LEN (1 << 30)
+
+// four consecutive values of a row at index i (a multiple of four); zero at and past len
+__device__ __forceinline__ void score_load4(const float* __restrict__ row, bool aligned, int i, int len, float v[4]) {
+    if (aligned && i + 4 <= len) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(row + i);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = i + k < len ? row[i + k] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ bool score_aligned(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// acc[0..NQ) of all 256 lanes -> dst[0..NQ): shuffle tree in the wave, waves 0..3 in order
+template <int NQ>
+__device__ __forceinline__ void score_reduce(double acc[NQ], double* __restrict__ dst) {
+    __shared__ double red[SCORE_THREADS / 64][NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+        for (int q = 0; q < NQ; ++q) red[wave][q] = acc[q];
+    __syncthreads();
+    if (threadIdx.x < NQ) {
+        double s = red[0][threadIdx.x];
+        for (int w = 1; w < SCORE_THREADS / 64; ++w) s += red[w][threadIdx.x];
+        dst[threadIdx.x] = s;
+    }
+}
+
+struct ScoreRows {
+    const float* p[3];            // estimate, clean, noisy
+    long long stride[3];          // floats between the rows of two utterances
+    int cap[3];                   // floats of a row that may be read
+};
+
+__device__ __forceinline__ int score_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+__global__ __launch_bounds__(SCORE_THREADS) void energy_partial_kernel(const ScoreRows rows, const int32_t* __restrict__ lens,
+                                                                       int spans, double* __restrict__ partial) {
+    const int b = blockIdx.y, span = blockIdx.x;
+    const int le = score_clamp(lens[3 * b], rows.cap[0]), ls = score_clamp(lens[3 * b + 1], rows.cap[1]),
+              ly = score_clamp(lens[3 * b + 2], rows.cap[2]);
+    const int longest = max(le, max(ls, ly));
+    if ((long long)span * SCORE_SPAN >= longest) return;          // (workgroup-uniform) the final kernel does not read this row
+    const float* e = rows.p[0] + (long long)b * rows.stride[0];
+    const float* s = rows.p[1] + (long long)b * rows.stride[1];
+    const float* y = rows.p[2] + (long long)b * rows.stride[2];
+    const bool ae = score_aligned(e), as = score_aligned(s), ay = score_aligned(y);
+    double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < SCORE_SPAN / (4 * SCORE_THREADS); ++j) {
+        const int i = span * SCORE_SPAN + j * 4 * SCORE_THREADS + 4 * (int)threadIdx.x;
+        if (i < longest) {
+            float ve[4], vs[4], vy[4];
+            score_load4(e, ae, i, le, ve);
+            score_load4(s, as, i, ls, vs);
+            score_load4(y, ay, i, ly, vy);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double de = (double)ve[k], ds = (double)vs[k], dn = (double)vy[k] - (double)vs[k];
+                acc[0] += de * de;
+                acc[1] += ds * ds;
+                acc[2] += dn * dn;
+                acc[3] += de * ds;
+                acc[4] += de * dn;
+                acc[5] += ds * dn;
+            }
+        }
+    }
+    score_reduce<6>(acc, partial + ((long long)b * spans + span) * 6);
+}
+
+__global__ void energy_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ lens, const ScoreRows rows,
+                                    int B, int spans, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int le = score_clamp(lens[3 * b], rows.cap[0]), ls = score_clamp(lens[3 * b + 1], rows.cap[1]),
+              ly = score_clamp(lens[3 * b + 2], rows.cap[2]);
+    const int longest = max(le, max(ls, ly));
+    const int used = (int)(((long long)longest + SCORE_SPAN - 1) / SCORE_SPAN);
+    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < used; ++k)
+        for (int q = 0; q < 6; ++q) a[q] += partial[((long long)b * spans + k) * 6 + q];
+    const double A = a[0], S = a[1], N = a[2], P = a[3], Q = a[4], R = a[5];
+    const double as = P / S, an = Q / N;                          // 0/0 = NaN for a silent clean or noise row, as in numpy
+    const double target = as * as * S, noise = an * an * N;
+    const double art = A + target + noise - 2.0 * as * P - 2.0 * an * Q + 2.0 * as * an * R;
+    const double resid = A - as * P + 0.0 * an;                   // (the reference's e_noise + e_art is NaN with a_n)
+    const double am = (S + R) / S;
+    double* o = out + (long long)b * 8;
+    o[0] = 10.0 * log10(target / resid);
+    o[1] = 10.0 * log10(target / noise);
+    o[2] = 10.0 * log10(target / art);
+    o[3] = 10.0 * log10((am * am * S) / (N - R * R / S));
+    o[4] = target;
+    o[5] = noise;
+    o[6] = art;
+    o[7] = resid;
+}
+
+extern "C" int eab_energy_ratios_f32(const float* est, long long est_stride, int est_cap, const float* clean,
+                                     long long clean_stride, int clean_cap, const float* noisy, long long noisy_stride,
+                                     int noisy_cap, const int32_t* lens, int B, double* partial, int partial_spans, double* out,
+                                     eab_stream_t stream) {
+    EAB_CHECK_ARG(est && clean && noisy && lens && partial && out && B > 0 && B <= 65535);
+    EAB_CHECK_ARG(est_cap > 0 && clean_cap > 0 && noisy_cap > 0);
+    EAB_CHECK_ARG(est_cap <= SCORE_MAX_LEN && clean_cap <= SCORE_MAX_LEN && noisy_cap <= SCORE_MAX_LEN);
+    // rows of two utterances must not overlap (B = 1 has no second row)
+    EAB_CHECK_ARG(B == 1 || (est_stride >= est_cap && clean_stride >= clean_cap && noisy_stride >= noisy_cap));
+    int cap = est_cap > clean_cap ? est_cap : clean_cap;
+    cap = cap > noisy_cap ? cap : noisy_cap;
+    const int spans = (cap + SCORE_SPAN - 1) / SCORE_SPAN;
+    EAB_CHECK_ARG(partial_spans >= spans);
+    ScoreRows rows;
+    rows.p[0] = est; rows.p[1] = clean; rows.p[2] = noisy;
+    rows.stride[0] = est_stride; rows.stride[1] = clean_stride; rows.stride[2] = noisy_stride;
+    rows.cap[0] = est_cap; rows.cap[1] = clean_cap; rows.cap[2] = noisy_cap;
+    hipLaunchKernelGGL(energy_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(SCORE_THREADS), 0, eab_stream(stream), rows,
+                       lens, partial_spans, partial);
+    hipLaunchKernelGGL(energy_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, eab_stream(stream), partial, lens, rows, B,
+                       partial_spans, out);
+    EAB_RETURN_LAUNCH_STATUS();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// per-utterance loss: esti [B][2][T_esti][F], label [B][2][T_label][F]; the valid bins of utterance b are i < frames[b]*F of a plane
+__global__ __launch_bounds__(SCORE_THREADS) void loss_lens_partial_kernel(const float* __restrict__ esti, const float* __restrict__ label,
+                                                                          const int32_t* __restrict__ frames, int T_esti, int T_label,
+                                                                          int T_max, int F, int spans, double* __restrict__ partial) {
+    const int b = blockIdx.y, span = blockIdx.x;
+    const int len = score_clamp(frames[b], T_max) * F;
+    if ((long long)span * SCORE_SPAN >= len) return;
+    const long long pe = (long long)T_esti * F, pl = (long long)T_label * F;
+    const float* er = esti + (long long)b * 2 * pe;
+    const float* lr = label + (long long)b * 2 * pl;
+    const float* ei = er + pe;
+    const float* li = lr + pl;
+    const bool a0 = score_aligned(er), a1 = score_aligned(ei), a2 = score_aligned(lr), a3 = score_aligned(li);
+    double acc[2] = {0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < SCORE_SPAN / (4 * SCORE_THREADS); ++j) {
+        const int i = span * SCORE_SPAN + j * 4 * SCORE_THREADS + 4 * (int)threadIdx.x;
+        if (i < len) {
+            float v0[4], v1[4], v2[4], v3[4];
+            score_load4(er, a0, i, len, v0);
+            score_load4(ei, a1, i, len, v1);
+            score_load4(lr, a2, i, len, v2);
+            score_load4(li, a3, i, len, v3);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {                         // (bins at and past len are zeros: they add +0.0)
+                const float me = sqrtf(v0[k] * v0[k] + v1[k] * v1[k]), ml = sqrtf(v2[k] * v2[k] + v3[k] * v3[k]);
+                const double dm = (double)(me - ml), dr = (double)(v0[k] - v2[k]), di = (double)(v1[k] - v3[k]);
+                acc[0] += dm * dm;
+                acc[1] += dr * dr + di * di;
+            }
+        }
+    }
+    score_reduce<2>(acc, partial + ((long long)b * spans + span) * 2);
+}
+
+__global__ void loss_lens_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ frames, int B, int T_max, int F,
+                                       int spans, double* __restrict__ out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int len = score_clamp(frames[b], T_max) * F;
+    const int used = (len + SCORE_SPAN - 1) / SCORE_SPAN;
+    double a = 0.0, c = 0.0;
+    for (int k = 0; k < used; ++k) {
+        a += partial[((long long)b * spans + k) * 2];
+        c += partial[((long long)b * spans + k) * 2 + 1];
+    }
+    out[b] = 0.5 * (a + 0.5 * c) / (double)len;                   // no frames: 0/0 = NaN, as the reference's empty mask
+}
+
+extern "C" int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* label, const int32_t* frames, int B, int T_esti,
+                                             int T_label, int F, double* partial, int partial_spans, double* loss,
+                                             eab_stream_t stream) {
+    EAB_CHECK_ARG(esti && label && frames && partial && loss && B > 0 && B <= 65535 && T_esti > 0 && T_label > 0 && F > 0);
+    const int T_max = T_esti < T_label ? T_esti : T_label;
+    EAB_CHECK_ARG((long long)T_max * F <= SCORE_MAX_LEN);
+    const int spans = (T_max * F + SCORE_SPAN - 1) / SCORE_SPAN;
+    EAB_CHECK_ARG(partial_spans >= spans);
+    hipLaunchKernelGGL(loss_lens_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(SCORE_THREADS), 0, eab_stream(stream), esti,
+                       label, frames, T_esti, T_label, T_max, F, partial_spans, partial);
+    hipLaunchKernelGGL(loss_lens_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, eab_stream(stream), partial, frames, B,
+                       T_max, F, partial_spans, loss);
+    EAB_RETURN_LAUNCH_STATUS();
+}

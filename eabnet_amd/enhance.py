@@ -137,8 +137,9 @@ class Enhancer:
         return plan
 
     # -- one batch -------------------------------------------------------------------
-    def _pack(self, waves, M: int, B: int, L: int, device: torch.device):
-        """the waves of a batch as one zero-padded (B, M, L) device buffer (+ the staging ring's event, or None)"""
+    def _pack(self, waves, M: int, B: int, L: int, device: torch.device, role: int = 0):
+        """the waves of a batch as one zero-padded (B, M, L) device buffer (+ the staging ring's event, or None); role: the
+        staging ring (``_HostStager.upload``) -- a second input of the batch keeps its own"""
         if all(w.is_cuda for w in waves):
             buf = torch.zeros((B, M, L), dtype=torch.float32, device=device)
             ev = None
@@ -147,7 +148,7 @@ class Enhancer:
             for k, w in enumerate(waves):
                 if not w.is_cuda:
                     host[k, :, :w.shape[1]] = w
-            buf, ev = _m._upload(host, device)
+            buf, ev = _m._upload(host, device, role)
         for k, w in enumerate(waves):
             if w.is_cuda:
                 buf[k, :, :w.shape[1]].copy_(w, non_blocking=True)
@@ -156,6 +157,12 @@ class Enhancer:
     def _model(self, spec: torch.Tensor, lengths) -> torch.Tensor:
         out = self.model(spec, lengths=lengths) if lengths is not None else self.model(spec)
         return out["esti_stft"] if isinstance(out, dict) else out
+
+    def _batch_done(self, batch: Batch, noisy, ev, est, wav, samples, counts, varlen: bool, device: torch.device) -> None:
+        """what a subclass adds to a batch, on the same stream, after its back end (eabnet_amd.score.Scorer): the packed noisy
+        (B, M, L) buffer and its staging event (already recorded after the front end; record it again after a later reader),
+        the model's final estimate (B, 2, T, F), the padded waves (B, hop * (T - 1)), and the sample and frame counts of all B
+        slots, dummies included (varlen False: one file on the exact-shape path)"""
 
     def _run(self, batch: Batch, waves, frames, device: torch.device, varlen: bool) -> List[torch.Tensor]:
         fft, hop = self.fft_num, self.hop
@@ -166,7 +173,10 @@ class Enhancer:
             spec = _m.stft_compress(buf, fft, hop, self.window)
             if ev is not None:
                 ev.record(torch.cuda.current_stream(device))
-            return [_m.istft(self._model(spec, None), fft, hop, self.window)[0]]
+            est = self._model(spec, None)
+            wav = _m.istft(est, fft, hop, self.window)
+            self._batch_done(batch, buf, ev, est, wav, [buf.shape[2]], [est.shape[2]], False, device)
+            return [wav[0]]
         B, T_max = batch.batch_size, frames[batch.indices[0]]
         # host waves: one buffer shape per (cap, batch size), so the staging ring is allocated once; device waves: no longer
         # than the longest file needs
@@ -186,6 +196,7 @@ class Enhancer:
         self._tick("istft")
         out = [wav[k, :hop * (counts[k] - 1)].clone() for k in range(len(mine))]
         self._tick("slice")
+        self._batch_done(batch, buf, ev, est, wav, samples, counts, True, device)
         return out
 
     @torch.no_grad()

@@ -1,0 +1,208 @@
+"""Score enhanced files on the device: the reference's evaluation loops (test.py:175-198 -- forward, istft, ``.cpu().numpy()``,
+``metrics.energy_ratios`` per file on the host; ``evaluate()`` of train_distributed.py:98-156, the same plus
+``com_mag_mse_loss`` per file) on the padded batches of ``Enhancer``.
+
+``energy_ratios`` and ``com_mag_mse_loss_per_utterance`` are the two kernels of csrc/score.hip behind tensor arguments;
+``Scorer`` is an ``Enhancer`` that also packs the clean waves, takes their label spectrum and fills one (N, 5) float64 device
+table -- si_sdr, si_sir, si_sar, si_sdr_mix, loss per file -- which it copies to the host once per call."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import model as _m
+from .enhance import Batch, Enhancer
+
+SPAN = 4096                                   # SCORE_SPAN of csrc/score.hip: samples (bins) per partial row
+METRICS = ("si_sdr", "si_sir", "si_sar", "si_sdr_mix", "loss")
+
+
+def _spans(n: int) -> int:
+    return max(1, -(-int(n) // SPAN))
+
+
+def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not t.is_cuda:
+        raise _lib.EabError("energy_ratios needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+    if t.dtype != torch.float32:
+        t = t.to(torch.float32)
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        t = t.contiguous()                    # rows are read in place when their samples are contiguous
+    return t
+
+
+def _check_lens3(lengths, B: int, widths: Tuple[int, int, int]) -> list:
+    """the checked sample counts of (est, clean, noisy), each a list or a device tensor; None: the full rows"""
+    if lengths is None:
+        lengths = [[w] * B for w in widths]
+    lengths = list(lengths)
+    if len(lengths) != 3:
+        raise ValueError(f"lengths must be a triple (est, clean, noisy) of (B,) counts, got {len(lengths)} members")
+    return [_m.check_lengths(l, B, w, lo=1, unit="the signal's row length", integral=True) for l, w in zip(lengths, widths)]
+
+
+def _lens3(cols: list, B: int, device: torch.device) -> torch.Tensor:
+    """checked counts as the (B, 3) int32 device array of the kernel"""
+    if not any(isinstance(c, torch.Tensor) for c in cols):
+        return _m._device_lengths([v for row in zip(*cols) for v in row], device).view(B, 3)
+    return torch.stack([_m._device_lengths(c, device) for c in cols], dim=1).contiguous()
+
+
+def energy_ratios(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, lengths=None, energies: bool = False) -> torch.Tensor:
+    """``metrics.energy_ratios(est, clean, noisy - clean)`` and ``metrics.si_sdr(clean, noisy)`` (reference metrics.py:14-39,
+    71-75) of B utterances in one launch: (B, Le), (B, Ls), (B, Ly) CUDA fp32 tensors -> a (B, 4) float64 device tensor
+    ``[si_sdr, si_sir, si_sar, si_sdr_mix]`` in dB (``energies=True``: (B, 8), followed by |s_target|^2, |e_noise|^2,
+    |e_art|^2, |e_noise + e_art|^2).
+
+    Rows may be strided views whose last dimension is contiguous (a channel of a (B, M, L) buffer, the first samples of a
+    wider buffer): they are read in place.  lengths: an optional triple of (B,) sample counts (sequences or integer tensors,
+    host or device) for (est, clean, noisy); every signal counts as zero from its own length up to the longest of the three, as
+    cal_single_metrics (test.py:126-138) pads them, and is never read there.  A silent clean or noise row gives NaN in its
+    own row.  All products and sums are fp64 in a fixed order: a row has the same bits alone and in any batch."""
+    for name, t in (("est", est), ("clean", clean), ("noisy", noisy)):
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be a (B, L) tensor, got {tuple(t.shape)}")
+    B = est.shape[0]
+    if clean.shape[0] != B or noisy.shape[0] != B:
+        raise ValueError(f"est, clean and noisy must hold the same number of rows, got {B}, {clean.shape[0]}, {noisy.shape[0]}")
+    cols = _check_lens3(lengths, B, (est.shape[1], clean.shape[1], noisy.shape[1]))
+    est, clean, noisy = _rows(est, "est"), _rows(clean, "clean"), _rows(noisy, "noisy")
+    if not (est.device == clean.device == noisy.device):
+        raise ValueError("est, clean and noisy must be on one device")
+    widths = (est.shape[1], clean.shape[1], noisy.shape[1])
+    lib = _lib.load()
+    with torch.cuda.device(est.device):
+        lens = _lens3(cols, B, est.device)
+        spans = _spans(max(widths))
+        partial = torch.empty((B, spans, 6), dtype=torch.float64, device=est.device)
+        out = torch.empty((B, 8), dtype=torch.float64, device=est.device)
+        args = []
+        for t in (est, clean, noisy):
+            args += [t.data_ptr(), t.stride(0) if B > 1 else t.shape[1], t.shape[1]]
+        _lib.check(lib.eab_energy_ratios_f32(*args, lens.data_ptr(), B, partial.data_ptr(), spans, out.data_ptr(),
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_energy_ratios_f32")
+    return out if energies else out[:, :4]
+
+
+def com_mag_mse_loss_per_utterance(esti: torch.Tensor, label: torch.Tensor, frame_list) -> torch.Tensor:
+    """(B,) float64 device tensor: ``com_mag_mse_loss(esti[b:b+1, :, :n_b], label[b:b+1, :, :n_b], [n_b])`` for every utterance
+    b of a padded batch, what ``evaluate()`` (reference train_distributed.py:98-156) takes file by file.  esti (B, 2, Te, F),
+    label (B, 2, Tl, F) CUDA tensors (the frame capacities may differ), frame_list (B,) counts in [1, min(Te, Tl)], host or
+    device; frames at and past n_b are never read.  Any B; value only (the training loss with its gradient is
+    ``com_mag_mse_loss``).  fp64 sums in a fixed order: an utterance has the same bits alone and in any batch."""
+    if esti.ndim != 4 or label.ndim != 4 or esti.shape[1] != 2 or label.shape[1] != 2 or esti.shape[0] != label.shape[0] \
+            or esti.shape[3] != label.shape[3]:
+        raise ValueError(f"expected (B,2,Te,F) and (B,2,Tl,F), got {tuple(esti.shape)} and {tuple(label.shape)}")
+    B, _, Te, F = esti.shape
+    Tl = label.shape[2]
+    frames = _m.check_lengths(frame_list, B, min(Te, Tl), lo=1, integral=True)
+    if not (esti.is_cuda and label.is_cuda):
+        raise _lib.EabError("com_mag_mse_loss_per_utterance needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+    lib = _lib.load()
+    e = esti.detach().to(torch.float32).contiguous()
+    lab = label.detach().to(device=e.device, dtype=torch.float32).contiguous()
+    with torch.cuda.device(e.device):
+        fr = _m._device_lengths(frames, e.device)
+        spans = _spans(min(Te, Tl) * F)
+        partial = torch.empty((B, spans, 2), dtype=torch.float64, device=e.device)
+        out = torch.empty((B,), dtype=torch.float64, device=e.device)
+        _lib.check(lib.eab_com_mag_mse_loss_lens_f32(e.data_ptr(), lab.data_ptr(), fr.data_ptr(), B, Te, Tl, F, partial.data_ptr(),
+                                                     spans, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                   "eab_com_mag_mse_loss_lens_f32")
+    return out
+
+
+class Scorer(Enhancer):
+    """``scores = Scorer(model)(noisy_waves, clean_waves)``: lists of (M, L_i) noisy and (L_i,) or (1, L_i) clean waves, host or
+    device -> a dict of (N,) float64 numpy arrays ``si_sdr, si_sir, si_sar, si_sdr_mix, loss`` in input order
+    (``return_waves=True``: ``(scores, waves)`` with exactly ``Enhancer``'s waves).
+
+    It runs ``Enhancer``'s plan and, per batch and on the same stream, packs the clean waves into a (B, 1, L) buffer through the
+    same staging path, takes ``stft_compress(clean, layout=1, lengths=samples)`` as the label, the per-utterance loss of the
+    model's final estimate against it (``com_mag_mse_loss_per_utterance``) and the energy ratios of (enhanced wave, clean,
+    noisy[ref_mic]) with the lengths (hop * (T_b - 1), L_b, L_b) (``energy_ratios``).  The rows go into one (N, 5) float64
+    device table at the files' input positions, dummy slots dropped; the table is copied to the host once, at the end of the
+    call -- nothing synchronises per file or per batch.  Non-causal models and files above the largest cap run one file at a
+    time through the same kernels at B = 1.  ``summary(scores)``: {metric: (mean, std)} with NaNs dropped (metrics.mean_std)."""
+
+    def __init__(self, model, max_batch: int = 16, fft_num: int = 320, hop: int = 160, window: Optional[torch.Tensor] = None,
+                 length_buckets="auto", ref_mic: int = 0):
+        super().__init__(model, max_batch, fft_num, hop, window, length_buckets)
+        if int(ref_mic) != ref_mic or ref_mic < 0:
+            raise ValueError(f"ref_mic must be a microphone index, got {ref_mic}")
+        self.ref_mic = int(ref_mic)
+        self._clean: List[torch.Tensor] = []
+        self._stage: Optional[torch.Tensor] = None
+        self._filled = 0
+
+    def _batch_done(self, batch: Batch, noisy, ev, est, wav, samples, counts, varlen: bool, device) -> None:
+        fft, hop = self.fft_num, self.hop
+        B, M, L = noisy.shape
+        cbuf, cev = self._pack([self._clean[i] for i in batch.indices], 1, B, L, device, role=1)
+        self._tick("pack_clean")
+        label = _m.stft_compress(cbuf, fft, hop, self.window, 1, lengths=samples if varlen else None)
+        self._tick("stft_clean")
+        loss = com_mag_mse_loss_per_utterance(est, label, counts)
+        ratios = energy_ratios(wav, cbuf[:, 0], noisy[:, self.ref_mic], lengths=([hop * (t - 1) for t in counts], samples, samples))
+        for e in (ev, cev):
+            if e is not None:                 # the staged noisy and clean waves have no reader after this point
+                e.record(torch.cuda.current_stream(device))
+        n = len(batch.indices)
+        rows = self._stage[self._filled:self._filled + n]
+        rows[:, :4].copy_(ratios[:n])
+        rows[:, 4].copy_(loss[:n])
+        self._filled += n
+        self._tick("score")
+
+    @torch.no_grad()
+    def __call__(self, noisy_waves: Sequence[torch.Tensor], clean_waves: Sequence[torch.Tensor], return_waves: bool = False):
+        noisy, clean = list(noisy_waves), list(clean_waves)
+        if len(noisy) != len(clean):
+            raise ValueError(f"Scorer: {len(noisy)} noisy files but {len(clean)} clean files")
+        clean = [c[None] if c.ndim == 1 else c for c in clean]
+        for k, (x, c) in enumerate(zip(noisy, clean)):
+            if c.ndim != 2 or c.shape[0] != 1:
+                raise ValueError(f"Scorer: clean waves must be (L,) or (1, L) tensors, file {k} is {tuple(c.shape)}")
+            if x.ndim != 2 or x.shape[1] != c.shape[1]:
+                raise ValueError(f"Scorer: file {k} has {tuple(x.shape)} noisy but {c.shape[1]} clean samples; the lengths must agree")
+            if self.ref_mic >= x.shape[0]:
+                raise ValueError(f"Scorer: ref_mic = {self.ref_mic} but file {k} has {x.shape[0]} microphones")
+        if self.model.training:
+            raise RuntimeError("Scorer: call model.eval() first")
+        N = len(noisy)
+        if N == 0:
+            super().__call__([])
+            scores = {m: np.zeros(0) for m in METRICS}
+            return (scores, []) if return_waves else scores
+        device = next(self.model.parameters()).device
+        if device.type != "cuda":
+            raise _lib.EabError("Scorer runs on MI355X only: move the model to 'cuda'. There is no CPU fallback by design.")
+        self._clean, self._filled = clean, 0
+        try:
+            with torch.cuda.device(device):
+                self._stage = torch.empty((N, 5), dtype=torch.float64, device=device)        # rows in plan order
+            waves = super().__call__(noisy)
+            assert self._filled == N
+            with torch.cuda.device(device):
+                order = [i for b in self.last_plan["batches"] for i in b["indices"]]
+                pos = torch.as_tensor(order, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+                table = torch.empty_like(self._stage).index_copy_(0, pos, self._stage)       # rows at the input positions
+                host = table.cpu().numpy()                                                   # the call's one device-to-host copy
+        finally:
+            self._clean, self._stage = [], None
+        scores = {m: np.ascontiguousarray(host[:, j]) for j, m in enumerate(METRICS)}
+        return (scores, waves) if return_waves else scores
+
+    @staticmethod
+    def summary(scores: Dict[str, np.ndarray]) -> Dict[str, Tuple[float, float]]:
+        """{metric: (mean, std)} with NaNs dropped, as metrics.mean_std (reference metrics.py:110-114)"""
+        out = {}
+        for m, v in scores.items():
+            v = np.asarray(v, dtype=np.float64)
+            v = v[~np.isnan(v)]
+            out[m] = (float(np.mean(v)), float(np.std(v))) if v.size else (float("nan"), float("nan"))
+        return out

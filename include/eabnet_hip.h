@@ -170,6 +170,33 @@ int eab_com_mag_mse_loss_f32(const float* esti, const float* label, const int32_
                              float* partial, int partial_blocks, float* loss, float* grad, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Evaluation scores per utterance of a padded batch (csrc/score.hip).  Replaces, one file at a time on the host,
+ * cal_single_metrics (test.py:126-153) -> metrics.energy_ratios / metrics.si_sdr, and the com_mag_mse_loss per file of
+ * evaluate() (train_distributed.py:98-156).  No struct and no earlier signature changes: EAB_ABI_VERSION stays 10.
+ *
+ * eab_energy_ratios_f32: energy_ratios(est, clean, noisy - clean) and si_sdr(clean, noisy) of B utterances.
+ *   est, clean, noisy: row b of a signal starts at base + b*stride (floats) and is read in place; at most `cap` floats of it
+ *   lens    DEVICE int32 [B][3]: samples of (est, clean, noisy) of utterance b, clamped to [0, cap]; a signal counts as zero
+ *           from its own length up to the longest of the three, and is never read there
+ *   partial device scratch of B * partial_spans * 6 doubles, partial_spans >= ceil(max(cap) / 4096)
+ *   out     device double [B][8]: si_sdr, si_sir, si_sar, si_sdr_mix (dB), |s_target|^2, |e_noise|^2, |e_art|^2,
+ *           |e_noise + e_art|^2.  A silent clean or noise row gives NaN in ITS row (numpy's 0/0 in the reference).
+ * Products and sums in fp64 over fixed spans of 4096 samples added in index order: the row of an utterance has the same
+ * bits alone and in any batch, whatever the strides and alignments (16-byte loads where the row's address allows).
+ *
+ * eab_com_mag_mse_loss_lens_f32: loss[b] = com_mag_mse_loss(esti[b:b+1, :, :n_b], label[b:b+1, :, :n_b], [n_b]), value only.
+ *   esti [B][2][T_esti][F], label [B][2][T_label][F];  frames: DEVICE int32 [B], clamped to [0, min(T_esti, T_label)];
+ *   frames >= n_b are never read; any B
+ *   partial device scratch of B * partial_spans * 2 doubles, partial_spans >= ceil(min(T_esti, T_label) * F / 4096)
+ *   loss    device double [B] (NaN for an utterance without frames)
+ * ------------------------------------------------------------------------ */
+int eab_energy_ratios_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
+                          int clean_cap, const float* noisy, long long noisy_stride, int noisy_cap, const int32_t* lens, int B,
+                          double* partial, int partial_spans, double* out, eab_stream_t stream);
+int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* label, const int32_t* frames, int B, int T_esti, int T_label,
+                                  int F, double* partial, int partial_spans, double* loss, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * K13  complex filter-and-sum, stand-alone.   Replaces EaBNet.py:114-117.
  *   w, x [B][T][F][M][2] -> y [B][2][T][F];  Y = sum_m W_m * X_m (no conjugate)
  * ------------------------------------------------------------------------ */
