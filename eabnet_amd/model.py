@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import os
 from collections import OrderedDict
 from typing import Dict, Optional, Tuple
 
@@ -23,7 +24,8 @@ import torch.nn as nn
 from . import _lib
 from . import program as prg
 from .graphs import LaneGraphs
-from .runtime import BoundProgram, graph_branches_allowed  # noqa: F401 (graph_branches_allowed: API)
+from .runtime import BoundProgram, chain_planner, chain_tables, encode, fuse_step
+from .runtime import graph_branches_allowed  # noqa: F401 (API)
 from .spec import GagConfig, NetConfig, ParamSpec, gag_param_specs, param_specs
 
 
@@ -95,7 +97,9 @@ class _Bound(BoundProgram):
         self.lens = torch.full((prog.B,), prog.T, dtype=torch.int32, device=device) if prog.varlen else None
         self.window = {"t_pos": self.t_pos.data_ptr() if prog.chunk else None, "chunk": prog.chunk,
                        "lens": self.lens.data_ptr() if prog.varlen else None}
-        self.exec_ops, self.n_exec, self.chains = None, 0, []
+        # a whole-program run of a streaming step: the fused launches (runtime.fuse_step) as [(op, first, count)] and their
+        # encoded array; None when the program has nothing to fuse.  self.ops keeps one entry per program op for partial runs.
+        self.fused, self.exec_ops = None, None
         self._carry_dev = None              # the carry table in device memory (eab_shift_desc[]), for the current binding
 
     def reset_counters(self) -> None:
@@ -130,18 +134,40 @@ class _Bound(BoundProgram):
     def bind(self, in_ptr: int, out_ptr: int, in2_ptr: Optional[int] = None) -> bool:
         if not super().bind(in_ptr, out_ptr, in2_ptr):
             return False
-        self._plan_chains()
         self._carry_dev = None
+        # the fused step follows the binding: the chain launch reads the encoded descriptors of the ops it stands for from
+        # device memory (arena 'chain').  EAB_ST_CHAIN=0 / EAB_CLN_STEP=0 keep the separate launches.
+        p = self.prog
+        if not p.chunk:
+            return True
+        self.fused, self.exec_ops = None, None
+        self.arenas.pop("chain", None)
+        fused = fuse_step(p.ops, p.chunk, os.environ.get("EAB_ST_CHAIN", "1") != "0", os.environ.get("EAB_CLN_STEP", "1") != "0",
+                          chain_planner(self.ops))
+        if len(fused) < len(p.ops):
+            tables = chain_tables(self.ops, fused)
+            if tables:
+                self.arenas["chain"] = torch.frombuffer(bytearray(tables), dtype=torch.uint8).to(self.device)
+            self.fused = fused
+            self.exec_ops = encode([op for op, _, _ in fused], self.bases(), **self.window)
         return True
+
+    @property
+    def chains(self) -> list:
+        """(first, count) of every run of program ops the bound step executes as one chain launch"""
+        return [(first, count) for op, first, count in (self.fused or []) if op.kind == prg.OP_CONV_CHAIN]
+
+    @property
+    def n_exec(self) -> int:
+        """launches of a whole-program run of the fused step (0: nothing fused, the program runs its own array)"""
+        return len(self.exec_ops) if self.exec_ops is not None else 0
 
     def upload_carry(self) -> None:
         """The carry table of a streaming program (prog.carry) as eab_shift_desc[] in device memory, for the boundary
         buffers the program is bound to: uploaded once per binding, like the descriptors of a chain launch."""
         if self._carry_dev is not None or not self.prog.carry:
             return
-        assert self._ptrs is not None, "bind the program first"
-        bases = {k: t.data_ptr() for k, t in self.arenas.items()}
-        bases.update(zip(self.BOUNDARY, self._ptrs))
+        bases = self.bases()
         descs = (_lib.ShiftDesc * len(self.prog.carry))()
         for d, (ref, row, rows) in zip(descs, self.prog.carry):
             d.ptr, d.row_floats, d.rows = bases[ref.arena] + 4 * ref.off, row, rows
@@ -170,90 +196,6 @@ class _Bound(BoundProgram):
                      for s in (in_shape, out_shape, in2_shape))
         self.bind(*(None if b is None else b.data_ptr() for b in bufs))
         return bufs, lambda: self.run(torch.cuda.current_stream().cuda_stream)
-
-    def _plan_chains(self) -> None:
-        """Streaming programs: runs of consecutive small-tile convolutions that give every utterance ONE tile (the S-TCN of a
-        frame-synchronous step) are executed by ONE launch (eab_conv_st_chain_run, csrc/conv_st.hip): one workgroup per
-        utterance walks the run's descriptors, which are uploaded to device memory here.  self.exec_ops = the op array of a
-        whole-program run with every such run replaced by its chain op (self.ops keeps one entry per program op for
-        single-op debug launches).  EAB_ST_CHAIN=0 keeps separate launches."""
-        import os
-        self.exec_ops, self.n_exec, self.chains = None, 0, []
-        if not self.prog.chunk:
-            return
-        lib = _lib.load()
-        ops = self.prog.ops
-        n = len(ops)
-        use_chain = os.environ.get("EAB_ST_CHAIN", "1") != "0"
-        # cLN, one frame per step: the statistics / scan / apply launches of a unit (eab_cln_stats_f32 = two launches, then
-        # eab_cln_apply_f32) become ONE launch (eab_cln_step_f32: one workgroup per utterance sums the new frame, advances the
-        # running sums and normalises the frame -- the same code paths, so the same bits).  EAB_CLN_STEP=0 keeps three launches.
-        fuse_cln = self.prog.chunk == 1 and os.environ.get("EAB_CLN_STEP", "1") != "0"
-        def plan(first, cnt):
-            descs = (_lib.ConvDesc * cnt)(*[self.ops[first + t].conv for t in range(cnt)])
-            codes = (C.c_int * cnt)()
-            lds, bf = C.c_int(0), C.c_int(0)
-            if lib.eab_conv_st_chain_plan(descs, cnt, codes, C.byref(lds), C.byref(bf)) != 0:
-                return None
-            return first, cnt, descs, codes, lds.value, bf.value
-        # every op on its own first (is it a single-tile launch of a form the chain kernel carries, and in which precision),
-        # then maximal runs of such ops, planned as a whole
-        single = [plan(k, 1) if (use_chain and ops[k].kind == prg.OP_CONV and ops[k].korder == prg.KORDER_FRAG) else None
-                  for k in range(n)]
-        runs = []                                       # (first, count, descs, codes, lds, bf)
-        k = 0
-        while k < n:
-            if single[k] is None:
-                k += 1
-                continue
-            j = k
-            while j < n and single[j] is not None and single[j][5] == single[k][5]:
-                j += 1
-            got = plan(k, j - k) if j - k >= 2 else None
-            if got:
-                runs.append(got)
-            k = j
-        def cln_pair(k):
-            a, b = ops[k], ops[k + 1] if k + 1 < n else None
-            return (fuse_cln and b is not None and a.kind == prg.OP_CLN_STATS and b.kind == prg.OP_CLN_APPLY and a.x == b.x
-                    and a.mr == b.mr and (a.B, a.T, a.P, a.C) == (b.B, b.T, b.P, b.C) and a.win and b.win and a.state is not None)
-        if not runs and not any(cln_pair(k) for k in range(n - 1)):
-            return
-        exec_list = []
-        k = 0
-        ri = 0
-        while k < n:
-            if cln_pair(k):
-                a, b = self.ops[k], self.ops[k + 1]
-                o = _lib.Op()
-                o.kind = prg.OP_CLN_STEP
-                for j in range(5):
-                    o.p[j] = a.p[j]                           # x, slope of the statistics, sums, state, mr
-                for j, src in enumerate((2, 3, 4, 5, 6)):
-                    o.p[5 + j] = b.p[src]                     # gain, bias, slope, add, y
-                o.i[0:5] = [b.i[0], b.i[1], b.i[2], b.i[3], b.i[4]]
-                o.f[0] = a.f[0]
-                o.win.pos, o.win.count = a.win.pos, a.win.count
-                exec_list.append(o)
-                k += 2
-                continue
-            if ri < len(runs) and runs[ri][0] == k:
-                first, cnt, descs, codes, lds, bf = runs[ri]
-                raw = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(self.device)
-                dev_codes = torch.tensor(list(codes), dtype=torch.int32, device=self.device)
-                self.chains.append((first, cnt, raw, dev_codes))          # keep the device copies alive
-                o = _lib.Op()
-                o.kind = prg.OP_CONV_CHAIN
-                o.p[0], o.p[1] = raw.data_ptr(), dev_codes.data_ptr()
-                o.i[0:4] = [cnt, int(self.prog.B), lds, bf]
-                exec_list.append(o)
-                k += cnt
-                ri += 1
-            else:
-                exec_list.append(self.ops[k])
-                k += 1
-        self.exec_ops = (_lib.Op * len(exec_list))(*exec_list)
-        self.n_exec = len(exec_list)
 
     def _launch(self, name: str, stream: int, first: int, n: int) -> None:
         if first == 0 and n == len(self.prog.ops) and self.exec_ops is not None:

@@ -26,16 +26,24 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from ._lib import MAX_TAPS       # (the ctypes mirrors size their tap arrays by it)
 from .spec import GagConfig, NetConfig, gag_param_specs, gate_key, param_specs, unet_decoder_layers, unet_encoder_layers
 
-# mirrors of the C enums (include/eabnet_hip.h)
+# mirrors of the C #defines (include/eabnet_hip.h: EAB_<name>); tests/test_cabi.py compares every value with the header
 XF_NONE, XF_NORM_PRELU, XF_PRELU_NORM = 0, 1, 2
 EPI_LINEAR, EPI_GLU, EPI_RELU, EPI_MULSIG, EPI_ADD, EPI_DUALGATE, EPI_PHASE2 = 0, 1, 2, 3, 4, 5, 6
 OP_CONV, OP_IN_FINALIZE, OP_NORM_ACT, OP_LSTM64, OP_BFW_FS, OP_MEMSET0, OP_GAG_PACK, OP_GAG_CRM = 1, 2, 3, 4, 5, 6, 7, 8
+OP_CONV_CHAIN = 9        # run-time only (runtime.fuse_step): a run of small-tile launches executed by one launch (csrc/conv_st.hip)
+# training programs (train.py, train_gag.py)
+(OP_GATHER, OP_IN_STATS, OP_TR_NORM_ACT, OP_NORM_BWD, OP_GLU_BWD, OP_GATE_FWD, OP_GATE_BWD, OP_ADD, OP_RELU_BWD, OP_COLSUM,
+ OP_FILTER_SUM, OP_FS_BWD, OP_LN_FWD, OP_LN_BWD, OP_LSTM_TRAIN, OP_LSTM_BWD) = range(16, 32)
+OP_WGRAD = 32            # train.WgradOp: weight gradient of a convolution
 OP_CLN_STATS, OP_CLN_APPLY, OP_GATE_ROWS = 33, 34, 35
-OP_CLN_STEP = 38         # run-time only (model._Bound._plan_chains): statistics + apply of a cLN unit for a one-frame streaming step in one launch
-OP_CONV_CHAIN = 9        # run-time only (model._Bound._plan_chains): a run of small-tile launches executed by one launch (csrc/conv_st.hip)
-OP_WGRAD = 32            # training only (train.WgradOp): weight gradient of a convolution
+OP_GAG_CRM_BWD, OP_CLN_BWD = 36, 37
+OP_CLN_STEP = 38         # run-time only (runtime.fuse_step): statistics + apply of a cLN unit for a one-frame streaming step in one launch
+NB_SUMS_ZEROED = 0x100   # mode-word flag of the norm backward: the caller has zero-filled the sums scratch
+NB_SUM_COPIES = 8        # the norm backward's reduce pass spreads its atomics over that many copies
+STORE_BF16 = 0x200       # mode-word flag: the op's output tensor is stored as bf16
 ACT_SIGMOID, ACT_TANH, ACT_RELU = 0, 1, 2
 GAG_PRE_LD = 324   # floats per (b, t) row of the interleaved previous estimate: 2*161 rounded up to a float4
 GAG_LIN_LD = 192   # 161 linear outputs padded to three 64-column tiles
@@ -46,7 +54,6 @@ KORDER_TAP, KORDER_CHUNK, KORDER_FRAG = 0, 1, 2
 # 768-deep first phase of the last decoder measured slower there than on 128-row tiles (C1: 2.89 vs 2.75 ms per utterance)
 ST_GLU_KMAX = 512
 PATCH_MAX = 352    # CG_PMAX in csrc/conv_gemm.hip
-MAX_TAPS = 16
 EPS_IN = 1e-5      # nn.InstanceNorm*d default (reference EaBNet.py:684,686)
 EPS_LN = 1e-5      # nn.LayerNorm default (reference EaBNet.py:598)
 ALIGN = 64         # floats: every arena allocation starts on a 256-byte boundary
@@ -248,7 +255,7 @@ class MemsetOp:
 @dataclass
 class GagPackOp:
     """two planar (B,2,T,F) inputs -> enc_in [B][T][F][4] = (in_r, in_i, pre_r, pre_i) and
-    pre [B][T][GAG_PRE_LD] (channel f*2+ri, zero padded)."""
+    pre [B][T][pre_ld] (channel f*2+ri, zero padded)."""
     inpt: Ref
     pre_x: Ref
     enc_in: Ref
@@ -256,6 +263,7 @@ class GagPackOp:
     B: int
     T: int
     F: int
+    pre_ld: int = GAG_PRE_LD             # floats per (b, t) row of pre (train_gag.PRE_LD in the training programs)
     win: bool = False
     name: str = ""
     kind: int = OP_GAG_PACK
@@ -264,7 +272,7 @@ class GagPackOp:
 @dataclass
 class GagCrmOp:
     """GlanceGazeModule tail (GaGNet.py:127-133): out = pre * act(g) + (r, i) per TF bin;
-    pre/pre_out [B][T][GAG_PRE_LD], g/r/i [B][T][GAG_LIN_LD], planar [B][2][T][F]."""
+    pre/pre_out [B][T][pre_ld], g/r/i [B][T][GAG_LIN_LD], planar [B][2][T][F]."""
     pre: Ref
     g: Ref
     r: Ref
@@ -275,6 +283,7 @@ class GagCrmOp:
     T: int
     F: int
     act: int
+    pre_ld: int = GAG_PRE_LD
     win: bool = False
     name: str = ""
     kind: int = OP_GAG_CRM
@@ -315,6 +324,46 @@ class ClnApplyOp:
     win: bool = False
     name: str = ""
     kind: int = OP_CLN_APPLY
+
+
+@dataclass
+class ClnStepOp:
+    """A (ClnStatsOp, ClnApplyOp) pair of a one-frame streaming step in one launch (eab_cln_step_f32; runtime.fuse_step)"""
+    x: Ref
+    stat_slope: Optional[Ref]
+    sums: Ref
+    state: Ref
+    mr: Ref
+    gain: Ref
+    bias: Ref
+    slope: Ref
+    add: Optional[Ref]
+    out: Ref
+    B: int
+    T: int
+    P: int
+    C: int
+    mode: int
+    eps: float
+    win: bool = True
+    name: str = ""
+    kind: int = OP_CLN_STEP
+
+
+@dataclass
+class ConvChainOp:
+    """A run of single-tile small-tile convolutions in one launch (eab_conv_st_chain_run; runtime.fuse_step).  descs: the
+    run's n encoded eab_conv_desc, codes: the planner's n kernel codes, both in the bound program's 'chain' arena
+    (runtime.chain_tables).  No time window of its own: every descriptor carries one."""
+    descs: Ref
+    codes: Ref
+    n: int
+    B: int
+    lds_bytes: int
+    bf16: int
+    plan: Tuple[int, ...] = ()           # the values behind `codes`
+    name: str = ""
+    kind: int = OP_CONV_CHAIN
 
 
 @dataclass

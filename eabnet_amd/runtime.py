@@ -11,7 +11,7 @@ import ctypes as C
 import functools
 import os
 import warnings
-from typing import Dict, Mapping, Optional, Sequence
+from typing import Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -42,8 +42,11 @@ _LAYOUT = {
     prg.ClnStatsOp: (("B", "T", "P", "C"), ("x", "slope", "sums", "state", "mr"), ("eps",)),
     prg.ClnApplyOp: (("B", "T", "P", "C", "mode"), ("x", "mr", "gain", "bias", "slope", "add", "out"), ()),
     prg.GateRowsOp: (("B", "T", "row"), ("a", "r", "z"), ()),
-    prg.GagPackOp: (("B", "T", "F", prg.GAG_PRE_LD), ("inpt", "pre_x", "enc_in", "pre"), ()),
-    prg.GagCrmOp: (("B", "T", "F", prg.GAG_PRE_LD, prg.GAG_LIN_LD, "act"), ("pre", "g", "r", "i", "pre_out", "planar"), ()),
+    prg.GagPackOp: (("B", "T", "F", "pre_ld"), ("inpt", "pre_x", "enc_in", "pre"), ()),
+    prg.GagCrmOp: (("B", "T", "F", "pre_ld", prg.GAG_LIN_LD, "act"), ("pre", "g", "r", "i", "pre_out", "planar"), ()),
+    prg.ClnStepOp: (("B", "T", "P", "C", "mode"),
+                    ("x", "stat_slope", "sums", "state", "mr", "gain", "bias", "slope", "add", "out"), ("eps",)),
+    prg.ConvChainOp: (("n", "B", "lds_bytes", "bf16"), ("descs", "codes"), ()),
 }
 
 
@@ -113,6 +116,86 @@ def encode(ops: Sequence, bases: Mapping[str, Optional[int]], t_pos: Optional[in
     return arr
 
 
+def _aligned(nfloats: int) -> int:
+    return nfloats + (-nfloats) % prg.ALIGN
+
+
+def fuse_step(ops: Sequence, chunk: int, chain: bool, cln_step: bool,
+              plan_chain: Callable[[int, int], Optional[Tuple[Sequence[int], int, int]]]) -> List[Tuple[object, int, int]]:
+    """The launches of a whole streaming step: ``[(op, first, count)]``, every entry standing for ``ops[first:first + count]``
+    (an op passed through: itself, count 1).
+      * ``chain``: runs of consecutive small-tile convolutions that give every utterance ONE tile (the S-TCN of a
+        frame-synchronous step) become one ConvChainOp (eab_conv_st_chain_run, csrc/conv_st.hip: one workgroup per utterance
+        walks the run's descriptors).  ``plan_chain(first, count)`` says whether the chain kernel carries that run as a whole:
+        (kernel code per op, LDS bytes, bf16?) or None.  Every candidate is asked on its own first, then the maximal runs of at
+        least two accepted ops of one precision.  The tables go to the 'chain' arena, in the order of chain_tables.
+      * ``cln_step``, one frame per step: the statistics / scan / apply launches of a cLN unit (eab_cln_stats_f32 = two
+        launches, then eab_cln_apply_f32) become one ClnStepOp (eab_cln_step_f32: one workgroup per utterance sums the new
+        frame, advances the running sums and normalises the frame -- the same code paths, so the same bits).
+    An offline program (chunk 0) is passed through."""
+    n = len(ops)
+    single = [plan_chain(k, 1) if chain and chunk and op.kind == prg.OP_CONV and op.korder == prg.KORDER_FRAG else None
+              for k, op in enumerate(ops)]
+
+    def cln_pair(k: int) -> bool:
+        a, b = ops[k], ops[k + 1] if k + 1 < n else None
+        return (cln_step and chunk == 1 and b is not None and a.kind == prg.OP_CLN_STATS and b.kind == prg.OP_CLN_APPLY
+                and a.x == b.x and a.mr == b.mr and (a.B, a.T, a.P, a.C) == (b.B, b.T, b.P, b.C) and a.win and b.win
+                and a.state is not None)
+    fused, k, table = [], 0, 0                  # table: floats of the 'chain' arena handed out
+    while k < n:
+        j = k
+        while j < n and single[j] is not None and single[j][2] == single[k][2]:
+            j += 1
+        got = plan_chain(k, j - k) if j - k >= 2 else None
+        if got:
+            codes, lds, bf16 = got
+            descs = table
+            table += _aligned((j - k) * C.sizeof(_lib.ConvDesc) // 4)
+            op = prg.ConvChainOp(descs=prg.Ref("chain", descs), codes=prg.Ref("chain", table), n=j - k, B=ops[k].B,
+                                 lds_bytes=lds, bf16=bf16, plan=tuple(codes), name=f"chain[{ops[k].name}..{ops[j - 1].name}]")
+            table += _aligned(j - k)
+            fused.append((op, k, j - k))
+        elif cln_pair(k):
+            a, b = ops[k], ops[k + 1]
+            op = prg.ClnStepOp(x=a.x, stat_slope=a.slope, sums=a.sums, state=a.state, mr=a.mr, gain=b.gain, bias=b.bias,
+                               slope=b.slope, add=b.add, out=b.out, B=b.B, T=b.T, P=b.P, C=b.C, mode=b.mode, eps=a.eps,
+                               name=b.name + "_step")
+            fused.append((op, k, 2))
+            j = k + 2
+        else:                                   # (a run the planner refuses as a whole stays separate launches)
+            j = max(j, k + 1)
+            fused += [(ops[t], t, 1) for t in range(k, j)]
+        k = j
+    return fused
+
+
+def chain_planner(arr) -> Callable:
+    """fuse_step's ``plan_chain`` for the encoded array ``arr`` of the same ops: the library's host-side planner
+    (eab_conv_st_chain_plan) on the encoded descriptors; it needs no device."""
+    lib = _lib.load()
+
+    def plan(first: int, count: int):
+        descs = (_lib.ConvDesc * count)(*[arr[first + t].conv for t in range(count)])
+        codes = (C.c_int * count)()
+        lds, bf16 = C.c_int(0), C.c_int(0)
+        if lib.eab_conv_st_chain_plan(descs, count, codes, C.byref(lds), C.byref(bf16)) != 0:
+            return None
+        return list(codes), lds.value, bf16.value
+    return plan
+
+
+def chain_tables(arr, fused: Sequence) -> bytes:
+    """The 'chain' arena of a fused list: per ConvChainOp the encoded ``conv`` members of ``arr`` (the per-op array of the
+    same binding) for its range, then its kernel codes, each at the Ref the op carries.  Empty without a chain."""
+    buf = bytearray()
+    for op, first, count in fused:
+        if op.kind == prg.OP_CONV_CHAIN:
+            buf += bytes(4 * op.descs.off - len(buf)) + b"".join(bytes(arr[first + t].conv) for t in range(count))
+            buf += bytes(4 * op.codes.off - len(buf)) + bytes((C.c_int * count)(*op.plan))
+    return bytes(buf)
+
+
 def graph_branches_allowed() -> bool:
     """Parallel branches (side streams) for programs that mark independent chains?  EAB_GRAPH_BRANCHES=0 runs every program
     on one stream.  (Rounds 1-3 also switched them off while a torch.distributed process group was alive: a hipGraph with
@@ -145,12 +228,18 @@ class BoundProgram:
         ptrs += (None,) * (len(self.BOUNDARY) - len(ptrs))
         if ptrs == self._ptrs:
             return False
-        bases = {k: t.data_ptr() for k, t in self.arenas.items()}
-        bases.update(zip(self.BOUNDARY, ptrs))
+        self._ptrs = ptrs
+        bases = self.bases()
         for name, ops in self.lists.items():
             encode(ops, bases, out=self.arrays[name], **self.window)
-        self._ptrs = ptrs
         return True
+
+    def bases(self) -> Dict[str, Optional[int]]:
+        """arena name -> base address for the current binding (encode's ``bases``)"""
+        assert self._ptrs is not None, "bind the program first"
+        bases = {k: t.data_ptr() for k, t in self.arenas.items()}
+        bases.update(zip(self.BOUNDARY, self._ptrs))
+        return bases
 
     def capture(self, *shapes) -> bool:
         """Capture every op list on static boundary buffers of ``shapes`` (BOUNDARY order; None = no such buffer): one

@@ -39,16 +39,11 @@ from . import _lib
 from . import program as prg
 from .runtime import BoundProgram
 from .program import ALIGN, EPS_IN, EPS_LN, Ref, conv_tiles, glu_row_order
+from .program import (NB_SUM_COPIES, NB_SUMS_ZEROED, OP_ADD, OP_CLN_BWD, OP_COLSUM, OP_FILTER_SUM, OP_FS_BWD, OP_GATE_BWD,  # noqa: F401
+                      OP_GATE_FWD, OP_GATHER, OP_GLU_BWD, OP_IN_STATS, OP_LN_BWD, OP_LN_FWD, OP_LSTM_BWD, OP_LSTM_TRAIN,
+                      OP_NORM_BWD, OP_RELU_BWD, OP_TR_NORM_ACT, OP_WGRAD, STORE_BF16, XF_NORM_PRELU, XF_PRELU_NORM)
 from .spec import NetConfig, gate_key, param_specs
 
-XF_NORM_PRELU, XF_PRELU_NORM = prg.XF_NORM_PRELU, prg.XF_PRELU_NORM
-(OP_GATHER, OP_IN_STATS, OP_TR_NORM_ACT, OP_NORM_BWD, OP_GLU_BWD, OP_GATE_FWD, OP_GATE_BWD, OP_ADD, OP_RELU_BWD, OP_COLSUM,
- OP_FILTER_SUM, OP_FS_BWD, OP_LN_FWD, OP_LN_BWD, OP_LSTM_TRAIN, OP_LSTM_BWD) = range(16, 32)
-OP_WGRAD = prg.OP_WGRAD
-OP_CLN_STATS, OP_CLN_APPLY, OP_CLN_BWD = prg.OP_CLN_STATS, prg.OP_CLN_APPLY, 37      # include/eabnet_hip.h EAB_OP_CLN_*
-NB_SUMS_ZEROED = 0x100   # include/eabnet_hip.h EAB_NB_SUMS_ZEROED
-NB_SUM_COPIES = 8        # include/eabnet_hip.h EAB_NB_SUM_COPIES: the reduce pass spreads its atomics over that many copies
-STORE_BF16 = 0x200       # include/eabnet_hip.h EAB_STORE_BF16: the op's output tensor is stored as bf16
 MLP_LD = 64          # the second Linear of w_dnn is run with its 2M rows padded to one 64-column tile
 TRAIN_BOUND_CACHE = 3   # bound training programs kept per module (LRU over (B, T, F, device, precision))
 
@@ -428,10 +423,10 @@ class TrainLowering:
         sums, mr = self.alloc(B * T * 4), self.alloc(B * T * 2)              # [B][T][2] doubles | (cum_mean, rstd)
         gimg, bimg, simg = self.idx(f"{norm}.norm.gain").reshape(C), self.idx(f"{norm}.norm.bias").reshape(C), self.idx(f"{act}.weight")
         gain, bias, slp = self.wadd(f"{norm}.norm.gain", gimg), self.wadd(f"{norm}.norm.bias", bimg), self.vec(f"{act}.weight")
-        self.fwd.append(GenOp(OP_CLN_STATS, [raw.ref, slp if mode == XF_PRELU_NORM else None, sums, None, mr], [B, T, P, C], [EPS_IN],
-                              name=name + ".cln_stats"))
-        self.fwd.append(GenOp(OP_CLN_APPLY, [raw.ref, mr, gain, bias, slp, add.ref if add else None, out.ref], [B, T, P, C, mode],
-                              name=name + ".cln"))
+        self.fwd.append(prg.ClnStatsOp(x=raw.ref, slope=slp if mode == XF_PRELU_NORM else None, sums=sums, state=None, mr=mr,
+                                       B=B, T=T, P=P, C=C, eps=EPS_IN, name=name + ".cln_stats"))
+        self.fwd.append(prg.ClnApplyOp(x=raw.ref, mr=mr, gain=gain, bias=bias, slope=slp, add=add.ref if add else None, out=out.ref,
+                                       B=B, T=T, P=P, C=C, mode=mode, name=name + ".cln"))
 
         def back():
             d = self.grad_of(out)

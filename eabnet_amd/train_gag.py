@@ -27,7 +27,6 @@ from .program import Ref, glu_row_order
 from .spec import GagConfig, gag_param_specs
 from .train import GenOp, TVar, TrainLowering, TrainProgram, _split64
 
-OP_GAG_PACK, OP_GAG_CRM, OP_GAG_CRM_BWD = prg.OP_GAG_PACK, prg.OP_GAG_CRM, 36
 PRE_LD = 384            # floats per (b, t) row of the interleaved previous estimate: 2*161 padded to a multiple of 64
 LIN_LD = prg.GAG_LIN_LD
 
@@ -119,7 +118,8 @@ class GagTrainLowering(TrainLowering):
         c = cfg.c
         enc_in = TVar(self.alloc(B * T * F * 4), F, 4, tr.Slot(), needs_grad=False)
         pre = TVar(self.alloc(B * T * PRE_LD), 1, PRE_LD, tr.Slot(), needs_grad=False)
-        self.fwd.append(GenOp(OP_GAG_PACK, [Ref("in"), Ref("in2"), enc_in.ref, pre.ref], [B, T, F, PRE_LD], name="pack"))
+        self.fwd.append(prg.GagPackOp(inpt=Ref("in"), pre_x=Ref("in2"), enc_in=enc_in.ref, pre=pre.ref, B=B, T=T, F=F, pre_ld=PRE_LD,
+                                      name="pack"))
         x = enc_in
         if cfg.is_u2:
             for i in range(4):
@@ -166,14 +166,14 @@ class GagTrainLowering(TrainLowering):
             self.cur_lane = 0
             self.mark("fwd", "join", [1, 2])
             nxt = TVar(self.alloc(B * T * PRE_LD), 1, PRE_LD, tr.Slot(), needs_grad=gi + 1 < cfg.q)
-            self.fwd.append(GenOp(OP_GAG_CRM, [pre.ref, gain.ref, lr.ref, li.ref, nxt.ref, Ref("out", gi * n_stage)],
-                                  [B, T, F, PRE_LD, LIN_LD, act], name=f"gags.{gi}.crm"))
+            self.fwd.append(prg.GagCrmOp(pre=pre.ref, g=gain.ref, r=lr.ref, i=li.ref, pre_out=nxt.ref, planar=Ref("out", gi * n_stage),
+                                         B=B, T=T, F=F, act=act, pre_ld=PRE_LD, name=f"gags.{gi}.crm"))
 
             def back(gi=gi, pre=pre, gain=gain, nxt=nxt, back_g=back_g, back_r=back_r, back_i=back_i):
                 n = B * T * LIN_LD
                 dg, dr, di = self.alloc(n), self.alloc(n), self.alloc(n)
                 dst, aux = self.grad_target(pre) if pre.needs_grad else (None, None)
-                self.bwd.append(GenOp(OP_GAG_CRM_BWD, [pre.ref, gain.ref, Ref("dout", gi * n_stage), nxt.slot.ref, aux, dg, dr, di, dst],
+                self.bwd.append(GenOp(prg.OP_GAG_CRM_BWD, [pre.ref, gain.ref, Ref("dout", gi * n_stage), nxt.slot.ref, aux, dg, dr, di, dst],
                                       [B, T, F, PRE_LD, LIN_LD, act], name=f"gags.{gi}.crm_bwd"))
                 self.mark("bwd", "fork", [1, 2])
                 back_g(dg)

@@ -26,6 +26,22 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.EXPORTS) == names, "ctypes binding and header disagree on the entry points"
 
 
+def test_python_mirrors_every_header_constant():
+    """Every EAB_(OP|EPI|XF|PREC|KORDER|ACT)_* #define of the header, and the limits and flag words beside them, has a Python
+    mirror of the same name (without the EAB_ prefix) and value: the op kinds and enums in program.py, the ABI version in
+    _lib.py.  No two op kinds share a value."""
+    from eabnet_amd import _lib, program
+    src = open(os.path.join(ROOT, "include", "eabnet_hip.h")).read()
+    defines = {n: int(v, 0) for n, v in re.findall(r"^#define\s+EAB_(\w+)\s+(0[xX][0-9a-fA-F]+|\d+)\b", src, flags=re.M)}
+    names = [n for n in defines if re.match(r"(OP|EPI|XF|PREC|KORDER|ACT)_", n)]
+    assert len(names) >= 50
+    for n in names + ["MAX_TAPS", "NB_SUMS_ZEROED", "NB_SUM_COPIES", "STORE_BF16"]:
+        assert getattr(program, n, None) == defines[n], f"program.{n} != EAB_{n} = {defines[n]}"
+    assert _lib.ABI_VERSION == defines["ABI_VERSION"] and _lib.MAX_TAPS == defines["MAX_TAPS"]
+    kinds = [defines[n] for n in names if n.startswith("OP_")]
+    assert len(set(kinds)) == len(kinds), "two EAB_OP_* share a value"
+
+
 def test_binding_handshake_and_error_strings():
     from eabnet_amd import _lib
     lib = _lib.load()                      # checks ABI version + struct sizes

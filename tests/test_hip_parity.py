@@ -975,8 +975,8 @@ def test_streaming_with_longer_gated_kernels_equals_offline(dev, k1, chunk):
 @pytest.mark.parametrize("precision", ["f32", "bf16"])
 def test_streaming_s_tcn_runs_as_one_chain_launch(dev, precision, monkeypatch):
     """A frame-synchronous step (BatchNorm norms, chunk <= 16) runs the 1-D convolutions of the whole S-TCN as ONE launch
-    (conv_st_chain_kernel: one workgroup per utterance walks the descriptors; model._Bound._plan_chains): the chain must
-    engage, cover every S-TCN launch, and give the bits of the separate launches (EAB_ST_CHAIN=0) and of the offline call."""
+    (conv_st_chain_kernel: one workgroup per utterance walks the descriptors; runtime.fuse_step, bound in model._Bound.bind):
+    the chain must engage, cover every S-TCN launch, and give the bits of the separate launches (EAB_ST_CHAIN=0) and of the offline call."""
     from eabnet_amd import program as prg
     B, T, chunk = 2, 32, 8
     x = torch.from_numpy(paramgen.make_spec_input(B, T, 161, 4, 610)).to(dev)
@@ -997,6 +997,57 @@ def test_streaming_s_tcn_runs_as_one_chain_launch(dev, precision, monkeypatch):
     (first, cnt, *_), = b1.chains
     assert first == stcn[0] and cnt == len(stcn) and b1.n_exec == len(b1.prog.ops) - cnt + 1
     assert torch.equal(y1, y0) and torch.equal(y1, off1) and torch.equal(off1, off0)
+
+
+def test_streaming_cln_units_run_as_one_step_launch(dev, monkeypatch):
+    """cLN, one frame per step: every (statistics, apply) pair of the program runs as ONE launch (eab_cln_step_f32;
+    runtime.fuse_step), EAB_CLN_STEP=0 keeps the separate launches, and both give the frames of the offline call bit for bit.
+    Two utterances: the step kernel runs one workgroup per utterance; twelve frames: the running sums carry something."""
+    from eabnet_amd import program as prg
+    B, T = 2, 12
+    x = torch.from_numpy(paramgen.make_spec_input(B, T, 161, 4, 611)).to(dev)
+
+    def run(fuse: bool):
+        monkeypatch.setenv("EAB_CLN_STEP", "1" if fuse else "0")
+        net = _model(4, 1240, dev, norm_type="cLN", p=2, q=2)
+        with torch.no_grad():
+            off = net(x)
+        st = net.stream_begin(B, T_max=T, chunk=1)
+        y = torch.cat([st.step(x[:, t:t + 1]) for t in range(T)], dim=2)
+        return off, y, st.bound
+    off1, y1, b1 = run(True)
+    off0, y0, b0 = run(False)
+    n_stats = sum(op.kind == prg.OP_CLN_STATS for op in b1.prog.ops)
+    assert n_stats > 0 and sum(op.kind == prg.OP_CLN_STEP for op, _, _ in b1.fused) == n_stats
+    assert len(b1.exec_ops) == len(b1.prog.ops) - n_stats
+    assert b0.fused is None and b0.exec_ops is None, "EAB_CLN_STEP=0 runs the program's own array"
+    assert torch.equal(y1, y0) and torch.equal(y1, off1) and torch.equal(off1, off0)
+
+
+def test_rebinding_a_streaming_program_refreshes_the_fused_step(dev):
+    """bind() to other boundary buffers re-encodes the fused array and the chain's descriptor table with the per-op array: the
+    same step on a second set of buffers writes the same bits there and leaves the first output alone."""
+    from eabnet_amd import program as prg
+    from eabnet_amd.model import _Bound
+    B, T, chunk = 2, 8, 4
+    net = _model(4, 201, dev, norm_type="BN", p=2, q=2)
+    prog = prg.lower(net.cfg, net._numpy_params(), B, T, 161, chunk=chunk)
+    bound = _Bound(prog, dev)
+    x = torch.from_numpy(paramgen.make_spec_input(B, T, 161, 4, 612)).to(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for _ in range(2):
+        xin, out = x.clone(), torch.full((B, 2, T, 161), float("nan"), device=dev)
+        assert bound.bind(xin.data_ptr(), out.data_ptr())
+        assert bound.chains, "the chain launch did not engage"
+        bound.t_pos.fill_(0)                                # position 0 reads no state
+        bound.run(stream)
+        torch.cuda.synchronize()
+        outs.append((xin, out, out.clone()))
+    (_, out1, first1), (_, out2, _) = outs
+    assert torch.isfinite(out2[:, :, :chunk]).all() and torch.isnan(out2[:, :, chunk:]).all()
+    assert torch.equal(out2[:, :, :chunk], out1[:, :, :chunk])
+    assert torch.equal(out1.view(torch.int32), first1.view(torch.int32)), "the second run wrote into the first binding's output"
 
 
 def test_streaming_variants_and_refusals(dev):
