@@ -20,8 +20,9 @@ Data layout: activations are channels-last
 """
 from __future__ import annotations
 
+import functools
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -379,6 +380,122 @@ class GateRowsOp:
     kind: int = OP_GATE_ROWS
 
 
+@dataclass(frozen=True)
+class Geometry:
+    """What one convolution launch gathers (the geometry fields of eab_conv_desc / eab_wgrad_desc):
+      out[t][ostride * o + ophase] = sum_j W_j . in[t + dt[j]][istride * o + ioff[j]],  o in [0, No),
+    input [T][Fin][C], output [T][Fout][N], reads outside the input are zeros.  taps[j] = index of tap j in the layer's
+    flattened (kt * kf) kernel: what pack_taps selects.  The constructors are the only places where these numbers are
+    spelled out; ConvOp and WgradOp are filled from a Geometry by conv_launch and train.TrainLowering.wgrad_op."""
+    Fin: int
+    Fout: int
+    No: int
+    ostride: int
+    ophase: int
+    istride: int
+    dt: Tuple[int, ...]
+    ioff: Tuple[int, ...]
+    taps: Tuple[int, ...]
+
+    @property
+    def ntaps(self) -> int:
+        return len(self.dt)
+
+    def kpad(self, channels: int) -> int:
+        """K extent of the packed weights: per tap, the source channels in whole 16-channel units"""
+        return self.ntaps * ((channels + 15) // 16) * 16
+
+    @staticmethod
+    def pointwise(F: int, dt: int = 0) -> "Geometry":
+        """1x1 layers, heads, Linear and LSTM products on F positions per frame (dt = -1: the recurrent product)"""
+        return Geometry(F, F, F, 1, 0, 1, (dt,), (0,), (0,))
+
+    @staticmethod
+    def temporal(dts: Sequence[int]) -> "Geometry":
+        """1-D convolution over time ([B][T][1][C]), one tap per time offset"""
+        return Geometry(1, 1, 1, 1, 0, 1, tuple(dts), (0,) * len(dts), tuple(range(len(dts))))
+
+    @staticmethod
+    def strided(Fin: int, kt: int, kf: int) -> "Geometry":
+        """causal Conv2d [(kt, kf), stride (1, 2)]: out[t][o] = sum_{a, c} W[a][c] . in[t + a - (kt-1)][2o + c]"""
+        tp = [(a, c) for a in range(kt) for c in range(kf)]
+        Fout = (Fin - kf) // 2 + 1
+        return Geometry(Fin, Fout, Fout, 1, 0, 2, tuple(a - (kt - 1) for a, _ in tp), tuple(c for _, c in tp),
+                        tuple(a * kf + c for a, c in tp))
+
+    @staticmethod
+    def transposed(Fin: int, kt: int, kf: int) -> Tuple["Geometry", "Geometry"]:
+        """ConvTranspose2d [(kt, kf), stride (1, 2)] with the last kt-1 rows dropped, in gather form, one launch per
+        output-column parity:  out[t][2o + ph] = sum_{a} sum_{c = ph, ph+2, ..} W[a][c] . in[t - a][o - (c-ph)/2]"""
+        Fout = (Fin - 1) * 2 + kf
+        tps = [[(a, c) for a in range(kt) for c in range(ph, kf, 2)] for ph in (0, 1)]
+        return tuple(Geometry(Fin, Fout, (Fout + 1 - ph) // 2, 2, ph, 1, tuple(-a for a, _ in tp),
+                              tuple(-(c - ph) // 2 for _, c in tp), tuple(a * kf + c for a, c in tp)) for ph, tp in enumerate(tps))
+
+    @staticmethod
+    def adjoint(geoms) -> List["Geometry"]:
+        """The data-gradient launches of a forward launch (or of the launches that together write one output, the phase
+        pair): convolutions over the output gradient dz [T][Fout][N] with the transposed weights (taps index those) that
+        write  dx[t][f] = sum over (o, j) with istride * o + ioff[j] = f of W_j^T . dz[t - dt[j]][ostride * o + ophase].
+        A strided input walk gives one launch per input-column residue, each with the taps that reach it (none for a
+        residue without taps or columns); a strided output walk gives ONE launch that reads dz strided."""
+        geoms = [geoms] if isinstance(geoms, Geometry) else list(geoms)
+        g = geoms[0]
+        assert all((h.Fin, h.Fout, h.ostride, h.istride) == (g.Fin, g.Fout, g.ostride, g.istride) for h in geoms)
+        assert (g.ostride == 1 or g.istride == 1) and (g.istride == 1 or len(geoms) == 1)
+        if g.istride == 1:
+            tp = sorted((h.taps[j], -h.dt[j], h.ophase - h.ostride * h.ioff[j]) for h in geoms for j in range(h.ntaps))
+            return [Geometry(g.Fout, g.Fin, g.Fin, 1, 0, g.ostride, tuple(d for _, d, _ in tp), tuple(i for _, _, i in tp),
+                             tuple(k for k, _, _ in tp))]
+        out = []
+        for p in range(g.istride):
+            tp = [j for j in range(g.ntaps) if (g.ioff[j] - p) % g.istride == 0]
+            No = (g.Fin - p + g.istride - 1) // g.istride
+            if No > 0 and tp:
+                out.append(Geometry(g.Fout, g.Fin, No, g.istride, p, 1, tuple(-g.dt[j] for j in tp),
+                                    tuple(-(g.ioff[j] - p) // g.istride for j in tp), tuple(g.taps[j] for j in tp)))
+        return out
+
+
+def tcm_taps(kd: int, dilation: int, causal: bool) -> List[int]:
+    """time offsets of an S-TCM's dilated convolution (EaBNet.py:550-553): all in the past when causal, centred otherwise"""
+    span = (kd - 1) * dilation
+    lead = span if causal else span // 2
+    return [j * dilation - lead for j in range(kd)]
+
+
+@dataclass(frozen=True)
+class Stats:
+    """InstanceNorm partials a launch leaves per tile: `nsets` sets (one per PReLU slope in `slopes`; (None, None) = of
+    the plain output) in `ref`, which holds `tiles` tiles per utterance, this launch's from `tile0` on.  ref None: none."""
+    ref: Optional[Ref]
+    tiles: int
+    nsets: int = 1
+    slopes: Tuple[Optional[Ref], Optional[Ref]] = (None, None)
+    tile0: int = 0
+
+
+def conv_launch(name: str, B: int, T: int, srcs: Sequence, w: Ref, bias: Optional[Ref], geom: Geometry, *, N: int, epi: int,
+                dst: Ref, bm: int, stats: Optional[Stats] = None, ph1: Optional[Tuple[Ref, Geometry]] = None, **fields) -> ConvOp:
+    """THE place a ConvOp is filled from a Geometry.  srcs: one or two tensors (.ref, .F, .C) read as one concatenation;
+    ph1 = (weights, geometry) of the second output-column phase of a small-tile launch; fields: the remaining ConvOp
+    fields by name (transforms, residual operands ...; absent = none)."""
+    s0, s1 = srcs[0], (srcs[1] if len(srcs) > 1 else None)
+    C0, C1 = s0.C, (s1.C if s1 else 0)
+    assert geom.Fin == s0.F and geom.ntaps <= MAX_TAPS
+    st = stats if stats is not None and stats.ref is not None else Stats(None, 0, 0)
+    kw = {**dict(xf0=None, xf1=None, slope0=None, slope1=None, xf_mode=XF_NONE, aux=None, dst_acc=None), **fields}
+    if ph1 is not None:
+        w1, g1 = ph1
+        assert (g1.Fin, g1.Fout, g1.ostride, g1.istride) == (geom.Fin, geom.Fout, geom.ostride, geom.istride) and g1.ntaps <= geom.ntaps
+        kw.update(ph1_w=w1, ph1_No=g1.No, ph1_ophase=g1.ophase, ph1_Kpad=g1.kpad(C0 + C1), ph1_dt=list(g1.dt), ph1_ioff=list(g1.ioff))
+    return ConvOp(src0=s0.ref, src1=s1.ref if s1 else None, C0=C0, C1=C1, w=w, bias=bias, N=N, Kpad=geom.kpad(C0 + C1), B=B, T=T,
+                  Fin=geom.Fin, Fout=geom.Fout, No=geom.No, ostride=geom.ostride, ophase=geom.ophase, istride=geom.istride,
+                  dt=list(geom.dt), ioff=list(geom.ioff), epi=epi, dst=dst,
+                  Cout=N // 2 if epi in (EPI_GLU, EPI_DUALGATE, EPI_PHASE2) else N, stats=st.ref, nsets=st.nsets,
+                  stat_slope0=st.slopes[0], stat_slope1=st.slopes[1], stat_tiles=st.tiles, stat_tile0=st.tile0, bm=bm, name=name, **kw)
+
+
 def conv_tiles(T: int, No: int, bm: int) -> int:
     return (T * No + bm - 1) // bm
 
@@ -401,13 +518,21 @@ def glu_row_order(N: int) -> np.ndarray:
     return (r % 64 // 32) * (N // 2) + (r // 64) * 32 + r % 32
 
 
+def unit_rows(N: int, glu: bool, frag: bool = False) -> Tuple[np.ndarray, int]:
+    """(packed row -> original row, output channels) of a 2-D unit's N convolution rows: a gated unit has N / 2 output
+    channels and its rows in glu_row_order, unless the small-tile kernel runs it (frag: pack_frag orders the rows)"""
+    return (glu_row_order(N) if glu and not frag else np.arange(N)), (N // 2 if glu else N)
+
+
 def pack_taps(w_nck: np.ndarray, taps_k: Sequence[int]) -> np.ndarray:
-    """w_nck: [N][C][ntaps_all] (taps flattened); taps_k: which flattened taps,
+    """w_nck: [N][C][ntaps_all] (taps flattened); taps_k: which flattened taps (Geometry.taps),
     in kernel order.  Returns [N][len(taps_k)*UPT*16] with unit layout
-    (tap, 16-channel block), zero padded."""
+    (tap, 16-channel block), zero padded.  An integer input is an index image of the training programs'
+    parameter gather: same layout, dtype kept, padded with -1 (= a zero operand)."""
     N, C, _ = w_nck.shape
     upt = (C + 15) // 16
-    out = np.zeros((N, len(taps_k), upt * 16), dtype=np.float32)
+    idx = np.issubdtype(w_nck.dtype, np.integer)
+    out = np.full((N, len(taps_k), upt * 16), -1 if idx else 0, dtype=w_nck.dtype if idx else np.float32)
     for j, k in enumerate(taps_k):
         out[:, j, :C] = w_nck[:, :, k]
     return out.reshape(N, -1)
@@ -470,9 +595,9 @@ class WeightArena:
 
     def __init__(self):
         self.chunks: List[np.ndarray] = []
-        self.chunks_by_name: Dict[str, np.ndarray] = {}
         self.size = 0
         self.index: Dict[str, Ref] = {}
+        self.entries: Dict[Ref, Tuple[str, np.ndarray]] = {}
 
     def add(self, name: str, arr: np.ndarray) -> Ref:
         if name in self.index:
@@ -481,12 +606,16 @@ class WeightArena:
         pad = (-flat.size) % ALIGN
         ref = Ref("w", self.size)
         self.chunks.append(flat)
-        self.chunks_by_name[name] = flat
+        self.entries.setdefault(ref, (name, flat))      # (an empty array shares its offset with the next entry)
         if pad:
             self.chunks.append(np.zeros(pad, dtype=np.float32))
         self.size += flat.size + pad
         self.index[name] = ref
         return ref
+
+    def behind(self, ref: Ref) -> Tuple[str, np.ndarray]:
+        """(name, flat array) of the entry at `ref`"""
+        return self.entries[ref]
 
     def flat(self) -> np.ndarray:
         return np.concatenate(self.chunks) if self.chunks else np.zeros(0, np.float32)
@@ -682,7 +811,6 @@ class Lowering:
 
     # -- generic conv emission -----------------------------------------------------
     def pick_bm(self, No: int) -> int:
-        import os
         if os.environ.get("EAB_BM"):                     # tuning knob
             return int(os.environ["EAB_BM"])
         return 128 if self.B * conv_tiles(self.T, No, 128) >= 2 * CUS else 64
@@ -703,19 +831,17 @@ class Lowering:
                 return bm
         return ok[-1]
 
-    def emit_conv(self, name: str, srcs: Sequence[Act], w: Ref, bias: Optional[Ref], N: int, Kpad: int,
-                  Fout: int, No: int, ostride: int, ophase: int, istride: int, dt, ioff, epi: int,
-                  dst: Ref, stats: Optional[Ref] = None, nsets: int = 0, stat_slopes=(None, None),
-                  stat_tiles: int = 0, stat_tile0: int = 0, bm: Optional[int] = None, aux: Optional[Ref] = None,
+    def emit_conv(self, name: str, srcs: Sequence[Act], w: Ref, bias: Optional[Ref], geom: Geometry, *, N: int, epi: int,
+                  dst: Ref, stats: Optional[Stats] = None, bm: Optional[int] = None, aux: Optional[Ref] = None,
                   dst_acc: Optional[Ref] = None, fin: Optional[dict] = None, slope1: Optional[Ref] = None,
-                  xf1: Optional[Ref] = None, patch_ok: bool = True, st: bool = False, ph1: Optional[dict] = None,
-                  p2_mask1: int = 0) -> ConvOp:
+                  xf1: Optional[Ref] = None, patch_ok: bool = True, st: bool = False,
+                  ph1: Optional[Tuple[Ref, Geometry]] = None, p2_mask1: int = 0) -> ConvOp:
         """fin = dict(stats, tiles, nsets, count, norms=[...]) asks the kernel to reduce the
         producer's InstanceNorm partials itself (single source, transform order from srcs[0].mode);
         slope1 (+ xf1 when the table is static) = second transform of the SAME source for EPI_DUALGATE.
-        st = small-tile kernel (KORDER_FRAG): `w` (and ph1["w"]) are [N][Kpad] in ORIGINAL row order and are re-packed in
-        fragment order here; ph1 = dict(w, Kpad, No, ophase, dt, ioff): second output-column phase in the same launch."""
-        assert 1 <= len(srcs) <= 2 and len(dt) == len(ioff) <= MAX_TAPS
+        st = small-tile kernel (KORDER_FRAG): `w` (and ph1's) are [N][Kpad] in ORIGINAL row order and are re-packed in
+        fragment order here; ph1 = (weights, geometry): second output-column phase in the same launch."""
+        assert 1 <= len(srcs) <= 2
         assert st or ph1 is None
         s0 = srcs[0]
         s1 = srcs[1] if len(srcs) == 2 else None
@@ -726,12 +852,12 @@ class Lowering:
             assert s0.F == s1.F and s0.C % 16 == 0
         C0, C1 = s0.C, (s1.C if s1 else 0)
         upt = (C0 + C1 + 15) // 16
-        assert Kpad == len(dt) * upt * 16
+        Kpad, No, ntaps = geom.kpad(C0 + C1), geom.No, geom.ntaps
+        positions = lambda rows: patch_positions(rows, No, s0.F, geom.istride, geom.dt, geom.ioff)      # noqa: E731
         bm = bm or self.pick_bm(No)
         # patch pipeline (input patch of a 16-channel chunk staged once, taps read it shifted): pays
         # when several taps re-read the same inputs; needs the patch of a tile to fit its LDS area
         korder = KORDER_TAP
-        ph1kw = {}
         if st:
             assert self.precision in ("f32", "bf16") and N in (64, 128, 256) and bm in (16, 32, 64)
             glu_st = epi == EPI_GLU                       # exact fp32 only; weights in passes of 320, not all resident
@@ -742,31 +868,28 @@ class Lowering:
             korder = KORDER_FRAG
             dual = epi in (EPI_DUALGATE, EPI_GLU)         # a wave owns value and gate of the same 16 channels
 
-            def frag(ref: Ref, K: int) -> Ref:
-                key = next(k for k, r in self.W.index.items() if r == ref)
-                return self.W.add(key + ".frag", pack_frag(self.W.chunks_by_name[key].reshape(N, K), dual))
-            w = frag(w, Kpad)
+            def frag(ref: Ref) -> Ref:
+                key, arr = self.W.behind(ref)
+                return self.W.add(key + ".frag", pack_frag(arr.reshape(N, -1), dual))
+            w = frag(w)
             if ph1 is not None:
-                assert ph1["Kpad"] == len(ph1["dt"]) * upt * 16 and ph1["Kpad"] <= Kpad
-                ph1kw = dict(ph1_w=frag(ph1["w"], ph1["Kpad"]), ph1_No=ph1["No"], ph1_ophase=ph1["ophase"], ph1_Kpad=ph1["Kpad"],
-                             ph1_dt=list(ph1["dt"]), ph1_ioff=list(ph1["ioff"]))
-                self.flops += 2 * self.B * self.T * ph1["No"] * N * len(ph1["dt"]) * (C0 + C1)
+                ph1 = (frag(ph1[0]), ph1[1])
+                self.flops += 2 * self.B * self.T * ph1[1].No * N * ph1[1].ntaps * (C0 + C1)
         patch_min_n = int(os.environ.get("EAB_PATCH_MIN_N", "128"))      # tuning knob
-        if (not st and self.patch and N >= patch_min_n and len(dt) >= 2 and s0.F > 1 and epi != EPI_DUALGATE and mode != XF_PRELU_NORM
+        if (not st and self.patch and N >= patch_min_n and ntaps >= 2 and s0.F > 1 and epi != EPI_DUALGATE and mode != XF_PRELU_NORM
                 and C0 % 4 == 0 and C1 % 4 == 0 and patch_ok):
             for cand in ((bm,) if bm == 64 else (128, 64)):
-                if patch_positions(cand, No, s0.F, istride, dt, ioff) <= PATCH_MAX:
+                if positions(cand) <= PATCH_MAX:
                     korder, bm_p = KORDER_CHUNK, cand
                     break
             if korder == KORDER_CHUNK and bm_p != bm:
                 korder = KORDER_TAP        # tile counts of the statistics were planned for bm
         if epi == EPI_PHASE2:              # phase pair of a transposed convolution: exists in the patch pipeline only
-            assert not st and N == 128 and patch_positions(bm, No, s0.F, istride, dt, ioff) <= PATCH_MAX and mode != XF_PRELU_NORM
+            assert not st and N == 128 and positions(bm) <= PATCH_MAX and mode != XF_PRELU_NORM
             korder = KORDER_CHUNK
         if korder == KORDER_CHUNK:
-            key = next(k for k, r in self.W.index.items() if r == w)
-            wt = self.W.chunks_by_name[key].reshape(N, len(dt), upt, 16)
-            w = self.W.add(key + ".chunk", np.ascontiguousarray(wt.transpose(0, 2, 1, 3)).reshape(N, Kpad))
+            key, arr = self.W.behind(w)
+            w = self.W.add(key + ".chunk", np.ascontiguousarray(arr.reshape(N, ntaps, upt, 16).transpose(0, 2, 1, 3)).reshape(N, Kpad))
         # f16x3 needs bounded operands: every source except the raw network input is either
         # instance-normalised or a sum of such tensors; the first conv stays on exact fp32.
         # bf16 (torch.autocast semantics for the reference's convolutions): same rule, weights stay plain fp32 in
@@ -774,9 +897,8 @@ class Lowering:
         lowp = self.precision != "f32" and s0.ref.arena != "in" and C0 % 4 == 0 and C1 % 4 == 0 and not any(s.raw for s in srcs)
         prec = PREC_CODE[self.precision] if lowp else PREC_F32
         if prec == PREC_F16X3:
-            key = next(k for k, r in self.W.index.items() if r == w)
-            wf = self.W.chunks_by_name[key].reshape(N, Kpad)
-            w = self.W.add(key + ".f16x3", pack_f16x3(wf))
+            key, arr = self.W.behind(w)
+            w = self.W.add(key + ".f16x3", pack_f16x3(arr.reshape(N, Kpad)))
         finkw = {}
         if fin is not None:
             assert s1 is None and s0.xf is None and mode != XF_NONE
@@ -786,20 +908,15 @@ class Lowering:
                          fin_eps=EPS_IN, fin_gamma0=g[0], fin_beta0=b[0],
                          fin_gamma1=g[1] if len(g) > 1 else None, fin_beta1=b[1] if len(b) > 1 else None)
         sl1 = slope1 if slope1 is not None else (s1.slope if s1 else None)
-        op = ConvOp(src0=s0.ref, src1=s1.ref if s1 else None, xf0=s0.xf, xf1=s1.xf if s1 else xf1,
-                    slope0=s0.slope, slope1=sl1, C0=C0, C1=C1, xf_mode=mode, w=w, bias=bias,
-                    N=N, Kpad=Kpad, B=self.B, T=self.T, Fin=s0.F, Fout=Fout, No=No, ostride=ostride, ophase=ophase,
-                    istride=istride, dt=list(dt), ioff=list(ioff), epi=epi, aux=aux, dst=dst, dst_acc=dst_acc,
-                    Cout=N // 2 if epi in (EPI_GLU, EPI_DUALGATE, EPI_PHASE2) else N, stats=stats, nsets=nsets,
-                    stat_slope0=stat_slopes[0], stat_slope1=stat_slopes[1], stat_tiles=stat_tiles,
-                    stat_tile0=stat_tile0, bm=bm, name=name, precision=prec, korder=korder, win=bool(self.chunk),
-                    p2_mask1=p2_mask1, **finkw, **ph1kw)
+        op = conv_launch(name, self.B, self.T, srcs, w, bias, geom, N=N, epi=epi, dst=dst, bm=bm, stats=stats, ph1=ph1,
+                         xf0=s0.xf, xf1=s1.xf if s1 else xf1, slope0=s0.slope, slope1=sl1, xf_mode=mode, aux=aux, dst_acc=dst_acc,
+                         precision=prec, korder=korder, win=bool(self.chunk), p2_mask1=p2_mask1, **finkw)
         self.ops.append(op)
         if epi == EPI_PHASE2:              # phase-1 columns take the masked taps only, and one column fewer when Fout is odd
             n1 = bin(p2_mask1).count("1")
-            self.flops += 2 * self.B * self.T * (N // 2) * (C0 + C1) * (No * len(dt) + (Fout // 2) * n1)
+            self.flops += 2 * self.B * self.T * (N // 2) * (C0 + C1) * (No * ntaps + (geom.Fout // 2) * n1)
         else:
-            self.flops += 2 * self.B * self.T * No * N * len(dt) * (C0 + C1)
+            self.flops += 2 * self.B * self.T * No * N * ntaps * (C0 + C1)
         return op
 
     def can_fuse_finalize(self, ops: Sequence[ConvOp]) -> bool:
@@ -856,88 +973,49 @@ class Lowering:
                 and all(a.C <= 128 for a in srcs if a.xf is not None))
 
     # -- 2-D units -------------------------------------------------------------------
-    def conv2d_fwd(self, name: str, srcs: Sequence[Act], wkey: str, glu: bool, norm: Optional[str], act: str,
-                   in_perm: Optional[np.ndarray] = None, add: Optional[Act] = None) -> Act:
-        """Strided causal Conv2d [(kt,kf), stride (1,2)] (+GLU) -> raw output with
-        norm+PReLU pending (norm=None: PReLU only).  Reference GateConv2d EaBNet.py:434-460 /
-        Conv2dunit :391-407."""
+    def conv2d(self, name: str, srcs: Sequence[Act], wkey: str, glu: bool, norm: Optional[str], act: str,
+               in_perm: Optional[np.ndarray] = None, summed: bool = False, add: Optional[Act] = None, *, transposed: bool) -> Act:
+        """A 2-D unit (+GLU) -> raw output with norm+PReLU pending (norm=None: PReLU only), on the kernel chosen here.
+        conv2d_fwd: strided causal Conv2d [(kt,kf), stride (1,2)], the launch of Geometry.strided (reference GateConv2d
+        EaBNet.py:434-460 / Conv2dunit :391-407).  conv2d_transposed: ConvTranspose2d [(kt,kf), stride (1,2)] + drop of
+        the last kt-1 rows, the phase pair of Geometry.transposed (GateConvTranspose2d EaBNet.py:463-490 + Chomp_T
+        :617-624 / Deconv2dunit :410-431)."""
         wkey = gate_key(self.P, wkey)
-        w = self.P[f"{wkey}.weight"]                       # (N, Cin, kt, kf)
-        N, Cin, kt, kf = w.shape
-        if in_perm is not None:
-            w = w[:, in_perm]
-        Fin = srcs[0].F
-        Fout = (Fin - kf) // 2 + 1
-        taps = [(a, c) for a in range(kt) for c in range(kf)]
-        st = (self.st_ok(srcs, N, glu) and kt * kf * ((Cin + 15) // 16) * 16 <= (ST_GLU_KMAX if glu else 256)
-              and self.st_small(Fout, glu))
-        # (small-tile kernel: rows stay in the convolution's own order, emit_conv packs them in fragment order)
-        order, tag = (glu_row_order(N), "packed") if glu and not st else (np.arange(N), "rows" if glu else "packed")
-        wp = pack_taps(w.reshape(N, Cin, kt * kf)[order], [a * kf + c for a, c in taps])
-        wref = self.W.add(f"{wkey}.weight#{tag}", wp)
-        bref = self.W.add(f"{wkey}.bias#{tag}", self.P[f"{wkey}.bias"][order])
-        Cout = N // 2 if glu else N
-        dst = self.alloc_act(Fout, Cout)
-        bm = self.pick_st_bm(Fout, N, wp.shape[1]) if st else self.pick_bm(Fout)
-        tiles = conv_tiles(self.T, Fout, bm)
-        cln = self.cln and norm is not None
-        xf = None if cln else self.fixed_norm(norm, Cout)
-        stats = self.alloc(self.B * tiles * Cout * 4) if (xf is None and not cln) else None
-        op = self.emit_conv(name, srcs, wref, bref, N, wp.shape[1], Fout, Fout, 1, 0, 2,
-                            [a - (kt - 1) for a, _ in taps], [c for _, c in taps],
-                            EPI_GLU if glu else EPI_LINEAR, dst, stats, 1 if stats else 0, (None, None),
-                            tiles if stats else 0, 0, bm, st=st)
-        if cln:
-            return self.cln_norm(name, dst, Fout, Cout, norm, f"{act}.weight", XF_NORM_PRELU, add)
-        if xf is None:
-            if self.can_fuse_finalize([op]):
-                xf, = self.fuse_finalize([op], Cout, [norm])
-            else:
-                xf, = self.emit_finalize(name + ".in", stats, Cout, 1, tiles, self.T * Fout, [norm])
-        return Act(dst, Fout, Cout, xf, self.vec(f"{act}.weight"), XF_NORM_PRELU)
-
-    def conv2d_transposed(self, name: str, srcs: Sequence[Act], wkey: str, glu: bool, norm: str, act: str,
-                          summed: bool = False, add: Optional[Act] = None) -> Act:
-        """ConvTranspose2d [(kt,kf), stride (1,2)] + drop of the last kt-1 rows
-        (+GLU) as two gather-form launches, one per output-column parity:
-          out[t][2o+ph] = sum_{kt} sum_{kf = ph, ph+2, ..} W[kt][kf] . in[t-kt][o-(kf-ph)/2]
-        Reference GateConvTranspose2d EaBNet.py:463-490 + Chomp_T :617-624 /
-        Deconv2dunit :410-431."""
-        wkey = gate_key(self.P, wkey)
-        w = self.P[f"{wkey}.weight"]                       # (Cin, N, kt, kf)
+        w = self.P[f"{wkey}.weight"]                       # (N, Cin, kt, kf); transposed: (Cin, N, kt, kf)
         if summed:
             # Skip_connect 'add' (EaBNet.py:499-500): W.(f(a) + g(b)) = [W | W].cat(f(a), g(b)) -- the two
             # sources keep their own pending transforms and the sum is never materialised
             w = np.concatenate([w] * len(srcs), axis=0)
-        Cin, N, kt, kf = w.shape
+        if transposed:
+            w = w.transpose(1, 0, 2, 3)
+        N, Cin, kt, kf = w.shape
         assert Cin == sum(s.C for s in srcs)
+        if in_perm is not None:
+            w = w[:, in_perm]
         Fin = srcs[0].F
-        Fout = (Fin - 1) * 2 + kf
-        No = [(Fout + 1) // 2, Fout // 2]
-        upt = (Cin + 15) // 16
-        st = (self.st_ok(srcs, N, glu) and len(range(0, kf, 2)) * kt * upt * 16 <= (ST_GLU_KMAX if glu else 256)
-              and self.st_small(No[0], glu))
-        order, tag = (glu_row_order(N), "packed") if glu and not st else (np.arange(N), "rows" if glu else "packed")
-        wn = np.ascontiguousarray(w.transpose(1, 0, 2, 3)).reshape(N, Cin, kt * kf)[order]
+        geoms = Geometry.transposed(Fin, kt, kf) if transposed else (Geometry.strided(Fin, kt, kf),)
+        Fout, No, Kpad = geoms[0].Fout, [g.No for g in geoms], geoms[0].kpad(Cin)
+        st = self.st_ok(srcs, N, glu) and Kpad <= (ST_GLU_KMAX if glu else 256) and self.st_small(No[0], glu)
+        # (small-tile kernel: rows stay in the convolution's own order, emit_conv packs them in fragment order)
+        order, Cout = unit_rows(N, glu, st)
+        tag = "rows" if glu and st else "packed"
+        wn = np.ascontiguousarray(w).reshape(N, Cin, kt * kf)[order]
+        # (weight-arena order, kept: a strided unit's weights lie in front of its bias and norm table, the phases' behind them)
+        def weights():
+            return [self.W.add(f"{wkey}.weight#{tag}" + (f".ph{g.ophase}" if transposed else ""), pack_taps(wn, g.taps)) for g in geoms]
+        wrefs = None if transposed else weights()
         bref = self.W.add(f"{wkey}.bias#{tag}", self.P[f"{wkey}.bias"][order])
-        Cout = N // 2 if glu else N
         dst = self.alloc_act(Fout, Cout)
-        bm = self.pick_st_bm(No[0] + No[1], N, len(range(0, kf, 2)) * kt * upt * 16) if st else self.pick_bm(No[0])
+        bm = self.pick_st_bm(sum(No), N, Kpad) if st else self.pick_bm(No[0])
         tiles = [conv_tiles(self.T, n, bm) for n in No]
-        cln = self.cln
+        cln = self.cln and norm is not None
         xf = None if cln else self.fixed_norm(norm, Cout)
         stats = self.alloc(self.B * sum(tiles) * Cout * 4) if (xf is None and not cln) else None
-        phase_ops = []
-        phases = []
-        for ph in (0, 1):
-            taps = [(a, c) for a in range(kt) for c in range(ph, kf, 2)]
-            wp = pack_taps(wn, [a * kf + c for a, c in taps])
-            wref = self.W.add(f"{wkey}.weight#{tag}.ph{ph}", wp)
-            phases.append(dict(w=wref, Kpad=wp.shape[1], No=No[ph], ophase=ph, dt=[-a for a, _ in taps],
-                               ioff=[-(c - ph) // 2 for _, c in taps]))
+        wrefs = wrefs or weights()
+        epi = EPI_GLU if glu else EPI_LINEAR
         # (InstanceNorm configurations only: BatchNorm / cLN programs can be streamed, and a streamed program must run the
         # kernels -- the summation orders -- of its offline twin; those keep one launch per phase)
-        fused = (not st and not glu and self.phase2 and self.patch and not self.chunk and not self.bn and not self.cln
+        fused = (transposed and not st and not glu and self.phase2 and self.patch and not self.chunk and not self.bn and not self.cln
                  and N == 64 and Cin % 4 == 0 and all(s.C % 4 == 0 for s in srcs))
         if fused:
             # ONE launch for both output-column phases on ONE staged input patch (EPI_PHASE2, conv_gemm.hip): virtual
@@ -945,6 +1023,7 @@ class Lowering:
             # over the union of the two phases' taps; a tap that only phase 0 uses has zero phase-1 rows, skipped in the kernel.
             # The input is fetched and transformed once instead of once per (phase, tap): 3 -> 1 for the (1,3) unit kernels.
             shifts = sorted({(a, c // 2) for a in range(kt) for c in range(kf)})      # (kt index, input shift o - fi)
+            geom2 = replace(geoms[0], dt=tuple(-a for a, _ in shifts), ioff=tuple(-sft for _, sft in shifts), taps=tuple(range(len(shifts))))
             wv = np.zeros((2 * N, Cin, len(shifts)), dtype=np.float32)
             mask1 = 0
             for j, (a, sft) in enumerate(shifts):
@@ -952,13 +1031,11 @@ class Lowering:
                 if 2 * sft + 1 < kf:
                     wv[N:, :, j] = wn[:, :, a * kf + 2 * sft + 1]                      # phase 1: kf = 2 * shift + 1
                     mask1 |= 1 << j
-            dts, ios = [-a for a, _ in shifts], [-sft for _, sft in shifts]
             bm_f = self.pick_bm(No[0])
-            fused = (mask1 & 1) == 1 and patch_positions(bm_f, No[0], Fin, 1, dts, ios) <= PATCH_MAX
+            fused = (mask1 & 1) == 1 and patch_positions(bm_f, No[0], Fin, 1, geom2.dt, geom2.ioff) <= PATCH_MAX
         if fused:
             order2 = glu_row_order(2 * N)
-            wp = pack_taps(wv[order2], list(range(len(shifts))))
-            wref = self.W.add(f"{wkey}.weight#phase2", wp)
+            wref = self.W.add(f"{wkey}.weight#phase2", pack_taps(wv[order2], geom2.taps))
             b2 = np.concatenate([self.P[f"{wkey}.bias"]] * 2)[order2]
             bref2 = self.W.add(f"{wkey}.bias#phase2", b2)
             bm = bm_f
@@ -966,29 +1043,27 @@ class Lowering:
             if stats is not None:              # re-plan the partials for the fused launch's tiles (the region above was the
                 self.act_size = stats.off      # most recent allocation: give it back)
                 stats = self.alloc(self.B * tiles[0] * Cout * 4)
-            phase_ops.append(self.emit_conv(name, srcs, wref, bref2, 2 * N, wp.shape[1], Fout, No[0], 2, 0, 1, dts, ios, EPI_PHASE2,
-                                            dst, stats, 1 if stats else 0, (None, None), tiles[0] if stats else 0, 0, bm,
-                                            p2_mask1=mask1))
+            ops = [self.emit_conv(name, srcs, wref, bref2, geom2, N=2 * N, epi=EPI_PHASE2, dst=dst,
+                                  stats=Stats(stats, tiles[0]), bm=bm, p2_mask1=mask1)]
         elif st:
             # small-tile kernel: both output-column phases in ONE launch (tiles of phase 0, then of phase 1, per utterance)
-            p0, p1 = phases
-            phase_ops.append(self.emit_conv(name, srcs, p0["w"], bref, N, p0["Kpad"], Fout, No[0], 2, 0, 1, p0["dt"], p0["ioff"],
-                                            EPI_GLU if glu else EPI_LINEAR, dst, stats, 1 if stats else 0, (None, None),
-                                            sum(tiles) if stats else 0, 0, bm, st=True, ph1=p1))
+            ops = [self.emit_conv(name, srcs, wrefs[0], bref, geoms[0], N=N, epi=epi, dst=dst, bm=bm, st=True,
+                                  stats=Stats(stats, sum(tiles)), ph1=(wrefs[1], geoms[1]) if transposed else None)]
         else:
-            for ph, q in enumerate(phases):
-                phase_ops.append(self.emit_conv(f"{name}.ph{ph}", srcs, q["w"], bref, N, q["Kpad"], Fout, No[ph], 2, ph, 1,
-                                                q["dt"], q["ioff"],
-                                                EPI_GLU if glu else EPI_LINEAR, dst, stats, 1 if stats else 0, (None, None),
-                                                sum(tiles) if stats else 0, (0 if ph == 0 else tiles[0]) if stats else 0, bm))
+            ops = [self.emit_conv(name + (f".ph{g.ophase}" if transposed else ""), srcs, wref, bref, g, N=N, epi=epi, dst=dst, bm=bm,
+                                  stats=Stats(stats, sum(tiles), tile0=g.ophase * tiles[0]))
+                   for g, wref in zip(geoms, wrefs)]
         if cln:
             return self.cln_norm(name, dst, Fout, Cout, norm, f"{act}.weight", XF_NORM_PRELU, add)
         if xf is None:
-            if self.can_fuse_finalize(phase_ops):
-                xf, = self.fuse_finalize(phase_ops, Cout, [norm])
+            if self.can_fuse_finalize(ops):
+                xf, = self.fuse_finalize(ops, Cout, [norm])
             else:
                 xf, = self.emit_finalize(name + ".in", stats, Cout, 1, sum(tiles), self.T * Fout, [norm])
         return Act(dst, Fout, Cout, xf, self.vec(f"{act}.weight"), XF_NORM_PRELU)
+
+    conv2d_fwd = functools.partialmethod(conv2d, transposed=False)
+    conv2d_transposed = functools.partialmethod(conv2d, transposed=True)
 
     def materialise(self, name: str, a: Act, b: Optional[Act] = None) -> Act:
         """out = f_a(a) [+ f_b(b)]: the En_unet_module residual (EaBNet.py:386)
@@ -1042,7 +1117,10 @@ class Lowering:
         cfg, T, B = self.cfg, self.T, self.B
         D, cd, kd = cfg.d_feat, cfg.cd1, cfg.kd1
         bn = self.bn                                   # BatchNorm eval: static tables, no statistics at all
-        Kd = kd * ((cd + 15) // 16) * 16
+        one = Geometry.pointwise(1)
+        # taps of the branch convolutions: z = left(y) * sigmoid(right(y))
+        gd = Geometry.temporal(tcm_taps(kd, dilation, cfg.is_causal))
+        Kd = gd.kpad(cd)
         use_st = (self.st and D == 256 and cd == 64 and conv_tiles(T, 1, 32) <= 64)
         if use_st:
             # small-tile kernel: 16- or 32-row tiles (2-4 x the workgroups of a 64-row launch, one memory round trip each)
@@ -1065,51 +1143,49 @@ class Lowering:
         else:
             # in_conv 1x1 (no bias); statistics of BOTH branch PReLUs of its output
             w_in = self.P[f"{pre}.in_conv.weight"][:, perm, :]               # (cd, D, 1)
-            wref = self.W.add(f"{pre}.in_conv.weight#packed", pack_taps(w_in, [0]))
+            wref = self.W.add(f"{pre}.in_conv.weight#packed", pack_taps(w_in, one.taps))
             y = self.alloc_act(1, cd)
             st = None if bn else self.alloc(B * tiles * 2 * cd * 4)
-            self.emit_conv(f"{pre}.in_conv", [x], wref, None, cd, D, 1, 1, 1, 0, 1, [0], [0], EPI_LINEAR, y,
-                           st, 0 if bn else 2, (None, None) if bn else (slL, slR), 0 if bn else tiles, 0, bm_in, st=use_st)
+            self.emit_conv(f"{pre}.in_conv", [x], wref, None, one, N=cd, epi=EPI_LINEAR, dst=y,
+                           stats=Stats(st, tiles, 2, (slL, slR)), bm=bm_in, st=use_st)
         assert bn or max(tiles, tiles_lr) <= 64, "in-kernel finalisation is sized for <= 64 partial tiles per utterance"
         # z = left(y) * sigmoid(right(y)): columns [0,cd) see PReLU_L/IN_L(y), columns [cd,2cd) PReLU_R/IN_R(y)
-        # taps (EaBNet.py:550-553): all in the past when causal, centred otherwise
-        span = (kd - 1) * dilation
-        lead = span if cfg.is_causal else span // 2
-        dts = [j * dilation - lead for j in range(kd)]
         wlr = np.concatenate([self.P[f"{pre}.left_conv.3.weight"], self.P[f"{pre}.right_conv.3.weight"]], axis=0)
         if use_st:     # rows stay in original order: emit_conv packs them in fragment order (value / gate blocks per wave)
-            wd = self.W.add(f"{pre}.lr_conv.weight#rows", pack_taps(wlr, range(kd)))
+            wd = self.W.add(f"{pre}.lr_conv.weight#rows", pack_taps(wlr, gd.taps))
         else:
-            wd = self.W.add(f"{pre}.lr_conv.weight#packed", pack_taps(wlr[glu_row_order(2 * cd)], range(kd)))
+            wd = self.W.add(f"{pre}.lr_conv.weight#packed", pack_taps(wlr[glu_row_order(2 * cd)], gd.taps))
         z = self.alloc_act(1, cd)
         st2 = None if bn else self.alloc(B * tiles_lr * cd * 4)
         slO = self.vec(f"{pre}.out_conv.0.weight")
         self.emit_conv(f"{pre}.lr_conv", [Act(y, 1, cd, self.bn_xf(nL) if bn else None, slL, XF_PRELU_NORM)], wd, None,
-                       2 * cd, Kd, 1, 1, 1, 0, 1, dts, [0] * kd, EPI_DUALGATE, z, st2,
-                       0 if bn else 1, (None, None) if bn else (slO, None), 0 if bn else tiles_lr, 0, bm_lr, slope1=slR,
-                       xf1=self.bn_xf(nR) if bn else None,
+                       gd, N=2 * cd, epi=EPI_DUALGATE, dst=z, stats=Stats(st2, tiles_lr, 1, (slO, None)),
+                       bm=bm_lr, slope1=slR, xf1=self.bn_xf(nR) if bn else None,
                        fin=None if bn else dict(stats=st, tiles=tiles, nsets=2, count=T, norms=[nL, nR]), st=use_st)
         w_out = self.P[f"{pre}.out_conv.2.weight"][perm]                  # (D, cd, 1), rows permuted
-        wo = self.W.add(f"{pre}.out_conv.2.weight#packed", pack_taps(w_out, [0]))
+        wo = self.W.add(f"{pre}.out_conv.2.weight#packed", pack_taps(w_out, one.taps))
         xn = self.alloc_act(1, D)
         op = self.emit_conv(f"{pre}.out_conv", [Act(z, 1, cd, self.bn_xf(nO) if bn else None, slO, XF_PRELU_NORM)], wo, None,
-                            D, cd, 1, 1, 1, 0, 1, [0], [0], EPI_ADD, xn, bm=bm_out, aux=x.ref, dst_acc=x_acc,
+                            one, N=D, epi=EPI_ADD, dst=xn, bm=bm_out, aux=x.ref, dst_acc=x_acc,
                             fin=None if bn else dict(stats=st2, tiles=tiles_lr, nsets=1, count=T, norms=[nO]), st=use_st)
         nxt = None
         if use_st and next_pre is not None and self.precision == "f32" and self.fuse_out_in:
-            # ... + the next block's in_conv on the rows just produced (one launch instead of two)
-            tiles_n = conv_tiles(T, 1, bm_out)
-            w_in_n = self.P[f"{next_pre}.in_conv.weight"][:, perm, :]
-            op.f2_w = self.W.add(f"{next_pre}.in_conv.weight#frag2", pack_frag(pack_taps(w_in_n, [0])))
-            op.f2_dst, op.f2_N = self.alloc_act(1, cd), cd
-            if not bn:
-                op.f2_stats, op.f2_nsets, op.f2_stat_tiles = self.alloc(B * tiles_n * 2 * cd * 4), 2, tiles_n
-                op.f2_stat_slope0 = self.vec(f"{next_pre}.left_conv.0.weight")
-                op.f2_stat_slope1 = self.vec(f"{next_pre}.right_conv.0.weight")
-            op.name = f"{pre}.out_conv+{next_pre}.in_conv"
-            self.flops += 2 * B * T * cd * D
-            nxt = dict(y=op.f2_dst, st=op.f2_stats, tiles=tiles_n)
+            nxt = self.fuse_next_in(op, next_pre, self.P[f"{next_pre}.in_conv.weight"][:, perm, :], conv_tiles(T, 1, bm_out),
+                                    [f"{next_pre}.left_conv.0.weight", f"{next_pre}.right_conv.0.weight"])
         return Act(xn, 1, D), nxt
+
+    def fuse_next_in(self, op: ConvOp, next_pre: str, w_in: np.ndarray, tiles: int, slopes: Sequence[str]) -> dict:
+        """... + the next block's in_conv on the rows an out_conv launch `op` has just produced (one launch instead of two),
+        with the statistics of the next block's PReLUs (`slopes`).  Returns the next block's `have_in`."""
+        cd = self.cfg.cd1
+        op.f2_w = self.W.add(f"{next_pre}.in_conv.weight#frag2", pack_frag(pack_taps(w_in, Geometry.pointwise(1).taps)))
+        op.f2_dst, op.f2_N = self.alloc_act(1, cd), cd
+        if not self.bn:
+            op.f2_stats, op.f2_nsets, op.f2_stat_tiles = self.alloc(self.B * tiles * len(slopes) * cd * 4), len(slopes), tiles
+            op.f2_stat_slope0, op.f2_stat_slope1 = ([self.vec(k) for k in slopes] + [None])[:2]
+        op.name = f"{op.name}+{next_pre}.in_conv"
+        self.flops += 2 * self.B * self.T * cd * self.cfg.d_feat
+        return dict(y=op.f2_dst, st=op.f2_stats, tiles=tiles)
 
     def tcm_cln(self, pre: str, x: Act, dilation: int, x_acc: Optional[Ref], perm: np.ndarray) -> Act:
         """SqueezedTCM.forward (EaBNet.py:572-578) with cumulative LayerNorms: every normalised tensor is materialised
@@ -1117,26 +1193,25 @@ class Lowering:
         cfg, T, B = self.cfg, self.T, self.B
         D, cd, kd = cfg.d_feat, cfg.cd1, cfg.kd1
         bm = 64
+        one = Geometry.pointwise(1)
         w_in = self.P[f"{pre}.in_conv.weight"][:, perm, :]
         y = self.alloc_act(1, cd)
-        self.emit_conv(f"{pre}.in_conv", [x], self.W.add(f"{pre}.in_conv.weight#packed", pack_taps(w_in, [0])), None, cd, D, 1, 1,
-                       1, 0, 1, [0], [0], EPI_LINEAR, y, bm=bm)
+        self.emit_conv(f"{pre}.in_conv", [x], self.W.add(f"{pre}.in_conv.weight#packed", pack_taps(w_in, one.taps)), None, one,
+                       N=cd, epi=EPI_LINEAR, dst=y, bm=bm)
         yL = self.cln_norm(f"{pre}.left", y, 1, cd, f"{pre}.left_conv.1", f"{pre}.left_conv.0.weight", XF_PRELU_NORM)
         yR = self.cln_norm(f"{pre}.right", y, 1, cd, f"{pre}.right_conv.1", f"{pre}.right_conv.0.weight", XF_PRELU_NORM)
-        span = (kd - 1) * dilation
-        dts = [j * dilation - span for j in range(kd)]              # causal (cLN is only built for is_causal=True)
-        Kp = kd * ((cd + 15) // 16) * 16
+        gd = Geometry.temporal(tcm_taps(kd, dilation, True))        # causal (cLN is only built for is_causal=True)
         a, r = self.alloc_act(1, cd), self.alloc_act(1, cd)
         for side, src, dst in (("left_conv", yL, a), ("right_conv", yR, r)):
-            wref = self.W.add(f"{pre}.{side}.3.weight#packed", pack_taps(self.P[f"{pre}.{side}.3.weight"], range(kd)))
-            self.emit_conv(f"{pre}.{side}", [src], wref, None, cd, Kp, 1, 1, 1, 0, 1, dts, [0] * kd, EPI_LINEAR, dst, bm=bm)
+            wref = self.W.add(f"{pre}.{side}.3.weight#packed", pack_taps(self.P[f"{pre}.{side}.3.weight"], gd.taps))
+            self.emit_conv(f"{pre}.{side}", [src], wref, None, gd, N=cd, epi=EPI_LINEAR, dst=dst, bm=bm)
         z = self.alloc_act(1, cd)
         self.ops.append(GateRowsOp(a=a, r=r, z=z, B=B, T=T, row=cd, win=bool(self.chunk), name=f"{pre}.gate"))
         zo = self.cln_norm(f"{pre}.out", z, 1, cd, f"{pre}.out_conv.1", f"{pre}.out_conv.0.weight", XF_PRELU_NORM)
         w_out = self.P[f"{pre}.out_conv.2.weight"][perm]
         xn = self.alloc_act(1, D)
-        self.emit_conv(f"{pre}.out_conv", [zo], self.W.add(f"{pre}.out_conv.2.weight#packed", pack_taps(w_out, [0])), None, D, cd, 1,
-                       1, 1, 0, 1, [0], [0], EPI_ADD, xn, bm=bm, aux=x.ref, dst_acc=x_acc)
+        self.emit_conv(f"{pre}.out_conv", [zo], self.W.add(f"{pre}.out_conv.2.weight#packed", pack_taps(w_out, one.taps)), None, one,
+                       N=D, epi=EPI_ADD, dst=xn, bm=bm, aux=x.ref, dst_acc=x_acc)
         return Act(xn, 1, D)
 
     # -- whole network ----------------------------------------------------------------------
@@ -1271,7 +1346,8 @@ class GagLowering(Lowering):
         cfg, T, B = self.cfg, self.T, self.B
         D, cd, kd = cfg.d_feat, cfg.cd1, cfg.kd1
         bn = self.bn
-        Kd = kd * ((cd + 15) // 16) * 16
+        one, gd = Geometry.pointwise(1), Geometry.temporal(tcm_taps(kd, dilation, cfg.is_causal))
+        Kd = gd.kpad(cd)
         use_st = self.st and D == 256 and cd == 64 and Kd <= 256 and conv_tiles(T, 1, 32) <= 64
         if use_st:     # small-tile kernel (see Lowering.tcm)
             mt = None if bn else 64
@@ -1285,37 +1361,26 @@ class GagLowering(Lowering):
         if have_in is not None:                         # produced by the previous block's fused out_conv launch
             y, st, tiles = have_in["y"], have_in["st"], have_in["tiles"]
         else:
-            wref = self.W.add(f"{pre}.in_conv.weight#packed", pack_taps(self.P[f"{pre}.in_conv.weight"], [0]))
+            wref = self.W.add(f"{pre}.in_conv.weight#packed", pack_taps(self.P[f"{pre}.in_conv.weight"], one.taps))
             y = self.alloc_act(1, cd)
             st = None if bn else self.alloc(B * tiles * cd * 4)
-            self.emit_conv(f"{pre}.in_conv", [x], wref, None, cd, D, 1, 1, 1, 0, 1, [0], [0], EPI_LINEAR, y,
-                           st, 0 if bn else 1, (None, None) if bn else (slD, None), 0 if bn else tiles, 0, bm, st=use_st)
-        span = (kd - 1) * dilation
-        lead = span if cfg.is_causal else span // 2
-        dts = [j * dilation - lead for j in range(kd)]
-        wd = self.W.add(f"{pre}.d_conv.3.weight#packed", pack_taps(self.P[f"{pre}.d_conv.3.weight"], range(kd)))
+            self.emit_conv(f"{pre}.in_conv", [x], wref, None, one, N=cd, epi=EPI_LINEAR, dst=y,
+                           stats=Stats(st, tiles, 1, (slD, None)), bm=bm, st=use_st)
+        wd = self.W.add(f"{pre}.d_conv.3.weight#packed", pack_taps(self.P[f"{pre}.d_conv.3.weight"], gd.taps))
         z = self.alloc_act(1, cd)
         st2 = None if bn else self.alloc(B * tiles_d * cd * 4)
-        self.emit_conv(f"{pre}.d_conv", [Act(y, 1, cd, self.bn_xf(nD) if bn else None, slD, XF_PRELU_NORM)], wd, None, cd,
-                       Kd, 1, 1, 1, 0, 1, dts, [0] * kd, EPI_LINEAR, z, st2, 0 if bn else 1,
-                       (None, None) if bn else (slO, None), 0 if bn else tiles_d, 0, bm_d,
+        self.emit_conv(f"{pre}.d_conv", [Act(y, 1, cd, self.bn_xf(nD) if bn else None, slD, XF_PRELU_NORM)], wd, None, gd,
+                       N=cd, epi=EPI_LINEAR, dst=z, stats=Stats(st2, tiles_d, 1, (slO, None)), bm=bm_d,
                        fin=None if bn else dict(stats=st, tiles=tiles, nsets=1, count=T, norms=[nD]), st=use_st)
-        wo = self.W.add(f"{pre}.out_conv.2.weight#packed", pack_taps(self.P[f"{pre}.out_conv.2.weight"], [0]))
+        wo = self.W.add(f"{pre}.out_conv.2.weight#packed", pack_taps(self.P[f"{pre}.out_conv.2.weight"], one.taps))
         xn = self.alloc_act(1, D)
         op = self.emit_conv(f"{pre}.out_conv", [Act(z, 1, cd, self.bn_xf(nO) if bn else None, slO, XF_PRELU_NORM)], wo, None,
-                            D, cd, 1, 1, 1, 0, 1, [0], [0], EPI_ADD, xn, bm=bm_out, aux=x.ref,
+                            one, N=D, epi=EPI_ADD, dst=xn, bm=bm_out, aux=x.ref,
                             fin=None if bn else dict(stats=st2, tiles=tiles_d, nsets=1, count=T, norms=[nO]), st=use_st)
         nxt = None
         tiles_n = conv_tiles(T, 1, bm_out)
         if use_st and next_pre is not None and self.precision == "f32" and self.fuse_out_in and (bn or tiles_n <= 64):
-            op.f2_w = self.W.add(f"{next_pre}.in_conv.weight#frag2", pack_frag(pack_taps(self.P[f"{next_pre}.in_conv.weight"], [0])))
-            op.f2_dst, op.f2_N = self.alloc_act(1, cd), cd
-            if not bn:
-                op.f2_stats, op.f2_nsets, op.f2_stat_tiles = self.alloc(B * tiles_n * cd * 4), 1, tiles_n
-                op.f2_stat_slope0 = self.vec(f"{next_pre}.d_conv.0.weight")
-            op.name = f"{pre}.out_conv+{next_pre}.in_conv"
-            self.flops += 2 * B * T * cd * D
-            nxt = dict(y=op.f2_dst, st=op.f2_stats, tiles=tiles_n)
+            nxt = self.fuse_next_in(op, next_pre, self.P[f"{next_pre}.in_conv.weight"], tiles_n, [f"{next_pre}.d_conv.0.weight"])
         return Act(xn, 1, D), nxt
 
     def chain(self, pre: str, x: Act) -> Act:
@@ -1336,12 +1401,12 @@ class GagLowering(Lowering):
         wk[:, :D] = w[:, feat_perm]
         wk[:, D:D + 2 * Fq] = w[:, cols_pre]
         order = glu_row_order(2 * D)
-        wref = self.W.add(f"{pfx}.in_conv#packed", pack_taps(wk[order][:, :, None], [0]))
+        one = Geometry.pointwise(1)
+        wref = self.W.add(f"{pfx}.in_conv#packed", pack_taps(wk[order][:, :, None], one.taps))
         bias = np.concatenate([self.P[f"{pfx}.in_conv_main.bias"], self.P[f"{pfx}.in_conv_gate.0.bias"]])[order]
         dst = self.alloc_act(1, D)
-        Kpad = ((D + GAG_PRE_LD + 15) // 16) * 16
-        self.emit_conv(f"{pfx}.in_conv", [feat, pre], wref, self.W.add(f"{pfx}.in_conv.bias#packed", bias), 2 * D, Kpad,
-                       1, 1, 1, 0, 1, [0], [0], EPI_GLU, dst, bm=64, patch_ok=False)
+        self.emit_conv(f"{pfx}.in_conv", [feat, pre], wref, self.W.add(f"{pfx}.in_conv.bias#packed", bias), one,
+                       N=2 * D, epi=EPI_GLU, dst=dst, bm=64, patch_ok=False)
         return Act(dst, 1, D)
 
     def linear(self, key: str, x: Act) -> Ref:
@@ -1351,8 +1416,9 @@ class GagLowering(Lowering):
         b = np.zeros(GAG_LIN_LD, np.float32)
         w[:Fq], b[:Fq] = self.P[f"{key}.weight"], self.P[f"{key}.bias"]
         dst = self.alloc_act(1, GAG_LIN_LD)
-        self.emit_conv(key, [x], self.W.add(f"{key}.weight#packed", pack_taps(w, [0])), self.W.add(f"{key}.bias#packed", b),
-                       GAG_LIN_LD, D, 1, 1, 1, 0, 1, [0], [0], EPI_LINEAR, dst, bm=64)
+        one = Geometry.pointwise(1)
+        self.emit_conv(key, [x], self.W.add(f"{key}.weight#packed", pack_taps(w, one.taps)), self.W.add(f"{key}.bias#packed", b),
+                       one, N=GAG_LIN_LD, epi=EPI_LINEAR, dst=dst, bm=64)
         return dst
 
     def build(self) -> Program:

@@ -27,6 +27,7 @@ path; what it does not cover (a gradient w.r.t. the input, eval-mode BatchNorm u
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -38,7 +39,7 @@ import torch
 from . import _lib
 from . import program as prg
 from .runtime import BoundProgram
-from .program import ALIGN, EPS_IN, EPS_LN, Ref, conv_tiles, glu_row_order
+from .program import ALIGN, EPS_IN, EPS_LN, Geometry, Ref, Stats, conv_tiles, pack_taps, unit_rows
 from .program import (NB_SUM_COPIES, NB_SUMS_ZEROED, OP_ADD, OP_CLN_BWD, OP_COLSUM, OP_FILTER_SUM, OP_FS_BWD, OP_GATE_BWD,  # noqa: F401
                       OP_GATE_FWD, OP_GATHER, OP_GLU_BWD, OP_IN_STATS, OP_LN_BWD, OP_LN_FWD, OP_LSTM_BWD, OP_LSTM_TRAIN,
                       OP_NORM_BWD, OP_RELU_BWD, OP_TR_NORM_ACT, OP_WGRAD, STORE_BF16, XF_NORM_PRELU, XF_PRELU_NORM)
@@ -303,71 +304,57 @@ class TrainLowering:
     def pick_bm(self, No: int) -> int:
         return 128 if self.B * conv_tiles(self.T, No, 128) >= 2 * prg.CUS else 64
 
-    @staticmethod
-    def pack_taps_idx(w_nck: np.ndarray, taps_k: Sequence[int]) -> np.ndarray:
-        N, Cc, _ = w_nck.shape
-        upt = (Cc + 15) // 16
-        out = np.full((N, len(taps_k), upt * 16), -1, dtype=np.int64)
-        for j, k in enumerate(taps_k):
-            out[:, j, :Cc] = w_nck[:, :, k]
-        return out.reshape(N, -1)
-
-    def conv_op(self, name, srcs: Sequence[TVar], w: Ref, bias: Optional[Ref], N: int, Kpad: int, Fin: int, Fout: int, No: int,
-                ostride: int, ophase: int, istride: int, dt, ioff, epi: int, dst: Ref, Cout: int, stats=None, stat_tiles=0,
-                stat_tile0=0, bm=None, aux=None, dst_acc=None, glu_dump=None, st: bool = False) -> prg.ConvOp:
+    def conv_op(self, name, srcs: Sequence[TVar], w: Ref, bias: Optional[Ref], geom: Geometry, *, N: int, epi: int, dst: Ref,
+                stats: Optional[Stats] = None, bm=None, aux=None, dst_acc=None, glu_dump=None, st: bool = False) -> prg.ConvOp:
         """st: `w` is in MFMA-fragment order and the launch goes to the small-tile kernel (csrc/conv_st.hip, KORDER_FRAG)"""
         s0, s1 = srcs[0], (srcs[1] if len(srcs) > 1 else None)
-        bm = bm or self.pick_bm(No)
-        op = prg.ConvOp(src0=s0.ref, src1=s1.ref if s1 else None, xf0=None, xf1=None, slope0=None, slope1=None,
-                        C0=s0.C, C1=s1.C if s1 else 0, xf_mode=prg.XF_NONE, w=w, bias=bias, N=N, Kpad=Kpad, B=self.B, T=self.T,
-                        Fin=Fin, Fout=Fout, No=No, ostride=ostride, ophase=ophase, istride=istride, dt=list(dt), ioff=list(ioff),
-                        epi=epi, aux=aux, dst=dst, dst_acc=dst_acc, Cout=Cout, stats=stats, nsets=1 if stats else 0,
-                        stat_slope0=None, stat_slope1=None, stat_tiles=stat_tiles, stat_tile0=stat_tile0, bm=bm, name=name)
-        op.glu_dump = glu_dump
+        op = prg.conv_launch(name, self.B, self.T, srcs, w, bias, geom, N=N, epi=epi, dst=dst, bm=bm or self.pick_bm(geom.No),
+                             stats=stats, aux=aux, dst_acc=dst_acc, glu_dump=glu_dump)
         if st:
             op.korder = prg.KORDER_FRAG
         if self.prec != prg.PREC_F32 and s0.ref.arena != "in" and s0.C % 4 == 0 and (s1 is None or s1.C % 4 == 0):
             op.precision = self.prec                  # the convolution on the raw network input stays exact
         self.emit.append(op)
-        fl = 2 * self.B * self.T * No * N * len(dt) * (s0.C + (s1.C if s1 else 0))
+        fl = 2 * self.B * self.T * geom.No * N * geom.ntaps * (op.C0 + op.C1)
         if self.emit is self.fwd:
             self.flops_fwd += fl
         else:
             self.flops_bwd += fl
         return op
 
-    def wgrad_op(self, name, dz: Ref, N: int, Fz: int, srcs: Sequence[TVar], No, ostride, ophase, istride, dt, ioff, gimg,
-                 dbias: Optional[Ref] = None) -> None:
+    def wgrad_op(self, name, dz: Ref, srcs: Sequence[TVar], geom: Geometry, gimg, *, N: int, dbias: Optional[Ref] = None) -> None:
+        """dW of the launch that read `srcs` with `geom` and N output channels, dz = gradient of its output; gimg: the
+        parameter-index image of its packed weights"""
         s0, s1 = srcs[0], (srcs[1] if len(srcs) > 1 else None)
         Ctot = s0.C + (s1.C if s1 else 0)
-        Kpad = len(dt) * ((Ctot + 15) // 16) * 16
+        Kpad = geom.kpad(Ctot)
         assert tuple(gimg.shape) == (N, Kpad), (gimg.shape, N, Kpad)
         # Weight gradients are leaves of the backward graph (nothing reads dW before the step ends; their operands -- the
         # finished gradient of a convolution output and a forward activation -- are never written again, no buffer is
         # recycled), so they are all emitted at the END of the backward program, sorted by geometry: eab_run_program
         # then serves every run of identical geometry (the 18 S-TCMs, the repeated U-Net levels) with one launch.
         self.deferred.append(WgradOp(dz=dz, src0=s0.ref, src1=s1.ref if s1 else None, dw=self.gadd([gimg]), N=N, C0=s0.C,
-                                     C1=s1.C if s1 else 0, Kpad=Kpad, B=self.B, T=self.T, Fin=s0.F, Fz=Fz, No=No,
-                                     ostride=ostride, ophase=ophase, istride=istride, dt=list(dt), ioff=list(ioff), name=name,
-                                     dbias=dbias, precision=self.prec if self.prec == prg.PREC_BF16 else prg.PREC_F32))
-        self.flops_bwd += 2 * self.B * self.T * No * N * len(dt) * Ctot
+                                     C1=s1.C if s1 else 0, Kpad=Kpad, B=self.B, T=self.T, Fin=s0.F, Fz=geom.Fout, No=geom.No,
+                                     ostride=geom.ostride, ophase=geom.ophase, istride=geom.istride, dt=list(geom.dt),
+                                     ioff=list(geom.ioff), name=name, dbias=dbias,
+                                     precision=self.prec if self.prec == prg.PREC_BF16 else prg.PREC_F32))
+        self.flops_bwd += 2 * self.B * self.T * geom.No * N * geom.ntaps * Ctot
 
     def colsum(self, name, x: Ref, rows: int, N: int, imgs: Sequence[np.ndarray]) -> None:
         self.bwd.append(GenOp(OP_COLSUM, [x, self.gadd(imgs)], list(_split64(rows)) + [N], name=name))
 
-    def dgrad(self, name: str, var: TVar, dz: Ref, Kd: int, Fz: int, launches: Sequence[tuple], st_bm: int = 0) -> None:
-        """grad(var) (+)= conv(dz; w) with the forward kernel on the gradient tensor dz [B][T][Fz][Kd]; `launches` =
-        (w, No, ostride, ophase, istride, dt, ioff) per launch -- the launches of one call write disjoint output
-        columns and share the accumulate operand."""
+    def dgrad(self, name: str, var: TVar, dz: Ref, launches: Sequence[Tuple[Ref, Geometry]], *, N: int, st_bm: int = 0) -> None:
+        """grad(var) (+)= conv(dz; w) with the forward kernel on the gradient tensor dz [B][T][Fin][N] of each geometry
+        (Geometry.adjoint of the forward launch); `launches` = (weights, geometry) per launch -- the launches of one call
+        write disjoint output columns and share the accumulate operand."""
         if not var.needs_grad or not launches:
             return
         dst, aux = self.grad_target(var)
-        src = TVar(dz, Fz, Kd)
         self.emit = self.bwd
-        for k, (w, No, ostride, ophase, istride, dt, ioff) in enumerate(launches):
-            self.conv_op(f"{name}.{k}", [src], w, None, var.C, len(dt) * ((Kd + 15) // 16) * 16, Fz, var.F, No, ostride, ophase,
-                         istride, dt, ioff, prg.EPI_ADD if aux is not None else prg.EPI_LINEAR, dst, var.C, aux=aux,
-                         st=st_bm > 0, bm=st_bm or None)
+        for k, (w, geom) in enumerate(launches):
+            assert geom.Fout == var.F
+            self.conv_op(f"{name}.{k}", [TVar(dz, geom.Fin, N)], w, None, geom, N=var.C,
+                         epi=prg.EPI_ADD if aux is not None else prg.EPI_LINEAR, dst=dst, aux=aux, st=st_bm > 0, bm=st_bm or None)
         self.emit = self.fwd
 
     # ---- norm + activation ---------------------------------------------------------------------------------
@@ -446,91 +433,39 @@ class TrainLowering:
             self.bn_layers.append((norm, mr.off + 2 * c0, C, n))
 
     # ---- 2-D units -----------------------------------------------------------------------------------------
-    def conv2d_fwd(self, name: str, srcs: Sequence[TVar], wkey: str, glu: bool, norm: str, act: str,
-                   in_perm: Optional[np.ndarray] = None, add: Optional[TVar] = None) -> TVar:
-        """Strided causal Conv2d (+GLU) + InstanceNorm + PReLU (GateConv2d EaBNet.py:434-460 / Conv2dunit :391-407)."""
+    def conv2d(self, name, srcs: Sequence[TVar], wkey: str, glu: bool, norm: str, act: str, in_perm: Optional[np.ndarray] = None,
+               add: Optional[TVar] = None, *, transposed: bool) -> TVar:
+        """A 2-D unit (+GLU) + InstanceNorm + PReLU.  conv2d_fwd: strided causal Conv2d, the launch of Geometry.strided
+        (GateConv2d EaBNet.py:434-460 / Conv2dunit :391-407); conv2d_transposed: ConvTranspose2d + chomp, the phase pair of
+        Geometry.transposed (EaBNet.py:463-490, 410-431).  The launches write one raw output; the backward is one weight
+        gradient per launch and, per source, the launches of Geometry.adjoint."""
         wkey = gate_key({f"{k}": 1 for k in self.specs}, wkey)
-        wi = self.idx(f"{wkey}.weight")                                      # (N, Cin, kt, kf) flat indices
+        wi = self.idx(f"{wkey}.weight")                                      # flat indices, as (N, Cin, kt, kf)
+        if transposed:
+            wi = wi.transpose(1, 0, 2, 3)
         N, Cin, kt, kf = wi.shape
+        assert Cin == sum(s.C for s in srcs)
         if in_perm is not None:
             wi = wi[:, in_perm]
-        Fin = srcs[0].F
-        Fout = (Fin - kf) // 2 + 1
-        order = glu_row_order(N) if glu else np.arange(N)
-        taps = [(a, c) for a in range(kt) for c in range(kf)]
-        wimg = self.pack_taps_idx(wi.reshape(N, Cin, kt * kf)[order], [a * kf + c for a, c in taps])
+        geoms = Geometry.transposed(srcs[0].F, kt, kf) if transposed else (Geometry.strided(srcs[0].F, kt, kf),)
+        tags = [str(g.ophase) for g in geoms] if transposed else [""]           # names: .ph0 / .ph1, .wgrad0 / .wgrad1
+        Fout = geoms[0].Fout
+        order, Cout = unit_rows(N, glu)
+        wn = np.ascontiguousarray(wi).reshape(N, Cin, kt * kf)[order]
+        wimgs = [pack_taps(wn, g.taps) for g in geoms]
         bimg = self.idx(f"{wkey}.bias")[order]
-        Cout = N // 2 if glu else N
+        if transposed:                                                       # (arena order: the bias, then the phases' weights)
+            self.wadd(f"{wkey}.b", bimg)
         raw = self.act(Fout, Cout)
-        bm = self.pick_bm(Fout)
-        tiles = conv_tiles(self.T, Fout, bm)
-        stats = self.alloc(self.B * tiles * Cout * 4) if (norm and not self.cln) else None
+        bm = self.pick_bm(geoms[0].No)
+        tiles = [conv_tiles(self.T, g.No, bm) for g in geoms]
+        stats = self.alloc(self.B * sum(tiles) * Cout * 4) if (norm and not self.cln) else None
         dump = self.alloc(self.B * self.T * Fout * N) if glu else None
-        dts, ios = [a - (kt - 1) for a, _ in taps], [c for _, c in taps]
-        self.conv_op(name, srcs, self.wadd(f"{wkey}.w", wimg), self.wadd(f"{wkey}.b", bimg), N, wimg.shape[1], Fin, Fout, Fout, 1, 0,
-                     2, dts, ios, prg.EPI_GLU if glu else prg.EPI_LINEAR, raw.ref, Cout, stats, tiles if stats else 0, 0, bm,
-                     glu_dump=dump)
-        xf, mr = self.finalize(name + ".in", stats, Cout, tiles, self.T * Fout, norm) if stats is not None else (None, None)
-        rows = self.B * self.T * Fout
-
-        def back():
-            dr = self.grad_of(raw)
-            if glu:
-                dz = self.alloc(rows * N)
-                self.bwd.append(GenOp(OP_GLU_BWD, [dr, dump, dz], list(_split64(rows)) + [N], name=name + ".glu_bwd"))
-            else:
-                dz = dr
-            self.wgrad_op(name + ".wgrad", dz, N, Fout, srcs, Fout, 1, 0, 2, dts, ios, wimg, dbias=self.gadd([bimg]))
-            # dgrad: per source, per input-column parity p:  dx[t'][2o'+p] = sum_{a, c = p, p+2, ..} W[:, ci, a, c]^T dz[t'+(kt-1)-a][o' - (c-p)/2]
-            c_lo = 0
-            for s in srcs:
-                launches = []
-                for p in (0, 1):
-                    tp = [(a, c) for a in range(kt) for c in range(p, kf, 2)]
-                    No = (Fin - p + 1) // 2
-                    if No <= 0 or not tp:
-                        continue
-                    wd = wi[order][:, c_lo:c_lo + s.C]                       # (N packed, C_s, kt, kf)
-                    img = self.pack_taps_idx(np.ascontiguousarray(wd.transpose(1, 0, 2, 3)).reshape(s.C, N, kt * kf),
-                                             [a * kf + c for a, c in tp])
-                    launches.append((self.wadd(f"{wkey}.wd.{c_lo}.{p}", img), No, 2, p, 1,
-                                     [(kt - 1) - a for a, _ in tp], [-(c - p) // 2 for _, c in tp]))
-                self.dgrad(f"{name}.dgrad", s, dz, N, Fout, launches)
-                c_lo += s.C
-        self.tape.append(back)          # before the norm/PReLU closure on the tape = after it in the backward
-        if self.cln and norm:
-            return self.cln_unit(name + ".act", raw, norm, act, XF_NORM_PRELU, add)
-        return self.norm_act(name + ".act", raw, norm, act, XF_NORM_PRELU, xf, mr, add)
-
-    def conv2d_transposed(self, name: str, srcs: Sequence[TVar], wkey: str, glu: bool, norm: str, act: str,
-                          add: Optional[TVar] = None) -> TVar:
-        """ConvTranspose2d (+chomp, +GLU) + InstanceNorm + PReLU as two gather-form launches (program.py), EaBNet.py:463-490, 410-431."""
-        wkey = gate_key({f"{k}": 1 for k in self.specs}, wkey)
-        wi = self.idx(f"{wkey}.weight")                                      # (Cin, N, kt, kf)
-        Cin, N, kt, kf = wi.shape
-        assert Cin == sum(s.C for s in srcs)
-        Fin = srcs[0].F
-        Fout = (Fin - 1) * 2 + kf
-        order = glu_row_order(N) if glu else np.arange(N)
-        wn = np.ascontiguousarray(wi.transpose(1, 0, 2, 3)).reshape(N, Cin, kt * kf)[order]
-        bimg = self.idx(f"{wkey}.bias")[order]
-        bref = self.wadd(f"{wkey}.b", bimg)
-        Cout = N // 2 if glu else N
-        raw = self.act(Fout, Cout)
-        Nos = [(Fout + 1) // 2, Fout // 2]
-        bm = self.pick_bm(Nos[0])
-        tiles = [conv_tiles(self.T, n, bm) for n in Nos]
-        stats = None if self.cln else self.alloc(self.B * sum(tiles) * Cout * 4)
-        dump = self.alloc(self.B * self.T * Fout * N) if glu else None
-        phases = []
-        for ph in (0, 1):
-            tp = [(a, c) for a in range(kt) for c in range(ph, kf, 2)]
-            wimg = self.pack_taps_idx(wn, [a * kf + c for a, c in tp])
-            dts, ios = [-a for a, _ in tp], [-(c - ph) // 2 for _, c in tp]
-            self.conv_op(f"{name}.ph{ph}", srcs, self.wadd(f"{wkey}.w.ph{ph}", wimg), bref, N, wimg.shape[1], Fin, Fout, Nos[ph], 2, ph,
-                         1, dts, ios, prg.EPI_GLU if glu else prg.EPI_LINEAR, raw.ref, Cout, stats, sum(tiles) if stats else 0,
-                         (0 if ph == 0 else tiles[0]) if stats else 0, bm, glu_dump=dump)
-            phases.append((ph, dts, ios, wimg))
+        for g, tag, wimg in zip(geoms, tags, wimgs):
+            ph = f".ph{tag}" if tag else ""
+            self.conv_op(name + ph, srcs, self.wadd(f"{wkey}.w{ph}", wimg), self.wadd(f"{wkey}.b", bimg), g, N=N,
+                         epi=prg.EPI_GLU if glu else prg.EPI_LINEAR, dst=raw.ref, bm=bm, glu_dump=dump,
+                         stats=Stats(stats, sum(tiles), tile0=g.ophase * tiles[0]))
         xf, mr = self.finalize(name + ".in", stats, Cout, sum(tiles), self.T * Fout, norm) if stats is not None else (None, None)
         rows = self.B * self.T * Fout
 
@@ -541,22 +476,22 @@ class TrainLowering:
                 self.bwd.append(GenOp(OP_GLU_BWD, [dr, dump, dz], list(_split64(rows)) + [N], name=name + ".glu_bwd"))
             else:
                 dz = dr
-            gb = self.gadd([bimg])               # both phases add their rows' column sums
-            for ph, dts, ios, wimg in phases:
-                self.wgrad_op(f"{name}.wgrad{ph}", dz, N, Fout, srcs, Nos[ph], 2, ph, 1, dts, ios, wimg, dbias=gb)
-            # dgrad: a strided convolution over dz:  dx[t'][f] = sum_{a, c} W[ci, :, a, c] dz[t'+a][2f + c]
-            taps = [(a, c) for a in range(kt) for c in range(kf)]
+            gb = self.gadd([bimg])               # every launch adds its rows' column sums
+            for g, tag, wimg in zip(geoms, tags, wimgs):
+                self.wgrad_op(f"{name}.wgrad{tag}", dz, srcs, g, wimg, N=N, dbias=gb)
             c_lo = 0
             for s in srcs:
-                wd = wi[c_lo:c_lo + s.C][:, order]                           # (C_s, N packed, kt, kf)
-                img = self.pack_taps_idx(wd.reshape(s.C, N, kt * kf), [a * kf + c for a, c in taps])
-                self.dgrad(f"{name}.dgrad", s, dz, N, Fout, [(self.wadd(f"{wkey}.wd.{c_lo}", img), Fin, 1, 0, 2,
-                                                              [a for a, _ in taps], [c for _, c in taps])])
+                wd = np.ascontiguousarray(wn[:, c_lo:c_lo + s.C].transpose(1, 0, 2))      # (C_s, N packed, kt * kf)
+                self.dgrad(f"{name}.dgrad", s, dz, [(self.wadd(f"{wkey}.wd.{c_lo}" + ("" if transposed else f".{g.ophase}"),
+                                                               pack_taps(wd, g.taps)), g) for g in Geometry.adjoint(geoms)], N=N)
                 c_lo += s.C
-        self.tape.append(back)
-        if self.cln:
+        self.tape.append(back)          # before the norm/PReLU closure on the tape = after it in the backward
+        if self.cln and norm:
             return self.cln_unit(name + ".act", raw, norm, act, XF_NORM_PRELU, add)
         return self.norm_act(name + ".act", raw, norm, act, XF_NORM_PRELU, xf, mr, add)
+
+    conv2d_fwd = functools.partialmethod(conv2d, transposed=False)
+    conv2d_transposed = functools.partialmethod(conv2d, transposed=True)
 
     def unet_module(self, pre: str, srcs: Sequence[TVar], scale: int, transposed: bool, in_perm=None) -> TVar:
         """En_unet_module.forward (EaBNet.py:372-388): the residual add is fused into the last norm+PReLU."""
@@ -596,12 +531,12 @@ class TrainLowering:
         return out
 
     # ---- 1-D units (S-TCM, Linear) -------------------------------------------------------------------------
-    def conv1d(self, name: str, src: TVar, wimg_nck: np.ndarray, dts: Sequence[int], bimg: Optional[np.ndarray], epi: int,
+    def conv1d(self, name: str, src: TVar, wimg_nck: np.ndarray, bimg: Optional[np.ndarray], geom: Geometry, *, epi: int,
                aux: Optional[TVar] = None, dst_acc: Optional[Ref] = None, wname: str = "") -> Tuple[TVar, Callable[[Ref], None]]:
-        """out[t] = sum_j W[:, :, j] src[t + dts[j]] (+ bias) with epilogue LINEAR / RELU / ADD(aux).  Returns the output
+        """out[t] = sum_j W[:, :, j] src[t + geom.dt[j]] (+ bias) with epilogue LINEAR / RELU / ADD(aux).  Returns the output
         and a function that, given the gradient w.r.t. the pre-epilogue sum, emits wgrad / dbias / dgrad."""
-        N, Cc, K = wimg_nck.shape
-        wimg = self.pack_taps_idx(wimg_nck, range(K))
+        N, Cc, _ = wimg_nck.shape
+        wimg = pack_taps(wimg_nck, geom.taps)
         out = self.act(1, N)
 
         def st_geometry(n, c, kp, epi_=prg.EPI_LINEAR):
@@ -613,17 +548,16 @@ class TrainLowering:
         st_bm = st_geometry(N, Cc, wimg.shape[1], epi)
         wref = self.wadd(wname + (".wf" if st_bm else ".w"), prg.pack_frag(wimg) if st_bm else wimg)
         bref = self.wadd(wname + ".b", bimg) if bimg is not None else None
-        self.conv_op(name, [src], wref, bref, N, wimg.shape[1], 1, 1, 1, 1, 0, 1, list(dts), [0] * K, epi, out.ref, N,
-                     bm=st_bm or 64, aux=aux.ref if aux is not None else None, dst_acc=dst_acc, st=st_bm > 0)
-        rows = self.B * self.T
+        self.conv_op(name, [src], wref, bref, geom, N=N, epi=epi, dst=out.ref, bm=st_bm or 64,
+                     aux=aux.ref if aux is not None else None, dst_acc=dst_acc, st=st_bm > 0)
 
         def back(dz: Ref):
-            self.wgrad_op(name + ".wgrad", dz, N, 1, [src], 1, 1, 0, 1, list(dts), [0] * K, wimg,
-                          dbias=self.gadd([bimg]) if bimg is not None else None)
-            img = self.pack_taps_idx(np.ascontiguousarray(wimg_nck.transpose(1, 0, 2)), range(K))      # (Cc, N, K)
+            self.wgrad_op(name + ".wgrad", dz, [src], geom, wimg, N=N, dbias=self.gadd([bimg]) if bimg is not None else None)
+            gd, = Geometry.adjoint(geom)
+            img = pack_taps(np.ascontiguousarray(wimg_nck.transpose(1, 0, 2)), gd.taps)      # (Cc, N, K)
             d_bm = st_geometry(Cc, N, img.shape[1])
-            self.dgrad(name + ".dgrad", src, dz, N, 1, [(self.wadd(wname + (".wdf" if d_bm else ".wd"), prg.pack_frag(img) if d_bm else img),
-                                                         1, 1, 0, 1, [-d for d in dts], [0] * K)], st_bm=d_bm)
+            self.dgrad(name + ".dgrad", src, dz, [(self.wadd(wname + (".wdf" if d_bm else ".wd"), prg.pack_frag(img) if d_bm else img), gd)],
+                       N=N, st_bm=d_bm)
         return out, back
 
     def in1d(self, name: str, raw: TVar, norm: str, act: str) -> TVar:
@@ -676,21 +610,18 @@ class TrainLowering:
         """SqueezedTCM.forward, EaBNet.py:572-578.  The closures go on the tape in forward order (they bind their
         operands late): in_conv | left norm | right norm | branch convs + gate | out norm | out_conv."""
         cfg = self.cfg
-        kd = cfg.kd1
         n = self.B * self.T * cfg.cd1
+        one, gd = Geometry.pointwise(1), Geometry.temporal(prg.tcm_taps(cfg.kd1, dilation, cfg.is_causal))
         w_in = self.idx(f"{pre}.in_conv.weight")[:, perm, :]                 # (cd, D, 1)
-        y, back_in = self.conv1d(f"{pre}.in_conv", x, w_in, [0], None, prg.EPI_LINEAR, wname=f"{pre}.in_conv")
+        y, back_in = self.conv1d(f"{pre}.in_conv", x, w_in, None, one, epi=prg.EPI_LINEAR, wname=f"{pre}.in_conv")
         self.tape.append(lambda: back_in(self.grad_of(y)))
         # both branch norms read y: one launch normalises it twice (eab_train_in1d_multi_f32, two contiguous outputs) and one
         # two-launch backward sums the two input gradients into dy
         yL, yR = self.in1d_multi(f"{pre}.lr", y, [f"{pre}.left_conv.1", f"{pre}.right_conv.1"],
                                  [f"{pre}.left_conv.0", f"{pre}.right_conv.0"])
-        span = (kd - 1) * dilation
-        lead = span if cfg.is_causal else span // 2
-        dts = [j * dilation - lead for j in range(kd)]
-        a, back_l = self.conv1d(f"{pre}.left_conv", yL, self.idx(f"{pre}.left_conv.3.weight"), dts, None, prg.EPI_LINEAR,
+        a, back_l = self.conv1d(f"{pre}.left_conv", yL, self.idx(f"{pre}.left_conv.3.weight"), None, gd, epi=prg.EPI_LINEAR,
                                 wname=f"{pre}.left_conv")
-        r, back_r = self.conv1d(f"{pre}.right_conv", yR, self.idx(f"{pre}.right_conv.3.weight"), dts, None, prg.EPI_LINEAR,
+        r, back_r = self.conv1d(f"{pre}.right_conv", yR, self.idx(f"{pre}.right_conv.3.weight"), None, gd, epi=prg.EPI_LINEAR,
                                 wname=f"{pre}.right_conv")
         z = self.act(1, cfg.cd1)
         self.fwd.append(GenOp(OP_GATE_FWD, [a.ref, r.ref, z.ref], list(_split64(n)), name=f"{pre}.gate"))
@@ -703,7 +634,7 @@ class TrainLowering:
         self.tape.append(back_gate)
         zo = self.in1d(f"{pre}.out", z, f"{pre}.out_conv.1", f"{pre}.out_conv.0")
         w_out = self.idx(f"{pre}.out_conv.2.weight")[perm]                   # (D, cd, 1), rows permuted
-        out, back_out = self.conv1d(f"{pre}.out_conv", zo, w_out, [0], None, prg.EPI_ADD, aux=x, dst_acc=x_acc,
+        out, back_out = self.conv1d(f"{pre}.out_conv", zo, w_out, None, one, epi=prg.EPI_ADD, aux=x, dst_acc=x_acc,
                                     wname=f"{pre}.out_conv")
 
         def back():
@@ -776,6 +707,7 @@ class TrainLowering:
         self.gtaps["de.4"] = e
 
         rows = B * T * F
+        pw = Geometry.pointwise(F)           # the heads, the MLP and the LSTM's input / recurrent products: 1x1 on every bin
         if cfg.bf_type == "cnn" or cfg.topo_type == "miso":
             # ---- pointwise head (EaBNet.py:80-81,111-113): Conv2d(64 -> 2M, 1x1); output plane m*2+ri is the column order the
             # filter-and-sum kernels read (rows padded to one 64-column tile).  miso (EaBNet.py:78-79,118-125): Conv2d(64 -> 2),
@@ -786,10 +718,10 @@ class TrainLowering:
             wc[:wk.shape[0]] = wk[:, :, None]
             bcimg = np.full(MLP_LD, -1, np.int64)
             bcimg[:wk.shape[0]] = self.idx("bf_map.bias")
-            wcimg = self.pack_taps_idx(wc, [0])
+            wcimg = pack_taps(wc, pw.taps)
             bw = self.act(F, MLP_LD)
-            self.conv_op("bf_map", [e], self.wadd("bf_map.w", wcimg), self.wadd("bf_map.b", bcimg), MLP_LD, 64, F, F, F, 1, 0, 1,
-                         [0], [0], prg.EPI_LINEAR, bw.ref, MLP_LD)
+            self.conv_op("bf_map", [e], self.wadd("bf_map.w", wcimg), self.wadd("bf_map.b", bcimg), pw, N=MLP_LD, epi=prg.EPI_LINEAR,
+                         dst=bw.ref)
             self.fwd.append(GenOp(OP_FILTER_SUM, [bw.ref, Ref("in"), Ref("out")], [B, T, F, M, MLP_LD], name="filter_sum"))
             self.gtaps["bf_w"] = bw
 
@@ -797,9 +729,9 @@ class TrainLowering:
                 dbw = self.alloc(rows * MLP_LD)
                 bw.slot.ref = dbw
                 self.bwd.append(GenOp(OP_FS_BWD, [Ref("dout"), Ref("in"), dbw], [B, T, F, M, MLP_LD], name="filter_sum.bwd"))
-                self.wgrad_op("bf_map.wgrad", dbw, MLP_LD, F, [e], F, 1, 0, 1, [0], [0], wcimg, dbias=self.gadd([bcimg]))
-                wcd = self.pack_taps_idx(np.ascontiguousarray(wc.transpose(1, 0, 2)), [0])      # (64 channels of e, 64 padded rows)
-                self.dgrad("bf_map.dgrad", e, dbw, MLP_LD, F, [(self.wadd("bf_map.wd", wcd), F, 1, 0, 1, [0], [0])])
+                self.wgrad_op("bf_map.wgrad", dbw, [e], pw, wcimg, N=MLP_LD, dbias=self.gadd([bcimg]))
+                wcd = pack_taps(np.ascontiguousarray(wc.transpose(1, 0, 2)), pw.taps)      # (64 channels of e, 64 padded rows)
+                self.dgrad("bf_map.dgrad", e, dbw, [(self.wadd("bf_map.wd", wcd), pw)], N=MLP_LD)
             self.tape.append(back_head_cnn)
             return self._finish_build()
 
@@ -823,18 +755,18 @@ class TrainLowering:
         # w_dnn: Linear 64->64 + ReLU, Linear 64->2M (rows padded to one 64-column tile), then the filter-and-sum
         w1 = self.idx("bf_map.w_dnn.0.weight")[:, :, None]
         y1 = self.act(F, 64)
-        w1img = self.pack_taps_idx(w1, [0])
+        w1img = pack_taps(w1, pw.taps)
         b1img = self.idx("bf_map.w_dnn.0.bias")
-        self.conv_op("bf_map.w_dnn.0", [h2], self.wadd("w_dnn.0.w", w1img), self.wadd("w_dnn.0.b", b1img), 64, 64, F, F, F, 1, 0, 1,
-                     [0], [0], prg.EPI_RELU, y1.ref, 64)
+        self.conv_op("bf_map.w_dnn.0", [h2], self.wadd("w_dnn.0.w", w1img), self.wadd("w_dnn.0.b", b1img), pw, N=64, epi=prg.EPI_RELU,
+                     dst=y1.ref)
         w2 = np.full((MLP_LD, 64, 1), -1, np.int64)
         w2[:2 * M] = self.idx("bf_map.w_dnn.2.weight")[:, :, None]
         b2img = np.full(MLP_LD, -1, np.int64)
         b2img[:2 * M] = self.idx("bf_map.w_dnn.2.bias")
-        w2img = self.pack_taps_idx(w2, [0])
+        w2img = pack_taps(w2, pw.taps)
         bw = self.act(F, MLP_LD)
-        self.conv_op("bf_map.w_dnn.2", [y1], self.wadd("w_dnn.2.w", w2img), self.wadd("w_dnn.2.b", b2img), MLP_LD, 64, F, F, F, 1, 0,
-                     1, [0], [0], prg.EPI_LINEAR, bw.ref, MLP_LD)
+        self.conv_op("bf_map.w_dnn.2", [y1], self.wadd("w_dnn.2.w", w2img), self.wadd("w_dnn.2.b", b2img), pw, N=MLP_LD,
+                     epi=prg.EPI_LINEAR, dst=bw.ref)
         self.fwd.append(GenOp(OP_FILTER_SUM, [bw.ref, Ref("in"), Ref("out")], [B, T, F, M, MLP_LD], name="filter_sum"))
 
         self.gtaps["bf_w"] = bw
@@ -845,28 +777,28 @@ class TrainLowering:
             dbw = self.alloc(rows * MLP_LD)
             bw.slot.ref = dbw
             self.bwd.append(GenOp(OP_FS_BWD, [Ref("dout"), Ref("in"), dbw], [B, T, F, M, MLP_LD], name="filter_sum.bwd"))
-            self.wgrad_op("w_dnn.2.wgrad", dbw, MLP_LD, F, [y1], F, 1, 0, 1, [0], [0], w2img, dbias=self.gadd([b2img]))
+            self.wgrad_op("w_dnn.2.wgrad", dbw, [y1], pw, w2img, N=MLP_LD, dbias=self.gadd([b2img]))
             dy1 = self.alloc(rows * 64)
             src = TVar(dbw, F, MLP_LD)
             self.emit = self.bwd
-            w2d = self.pack_taps_idx(np.ascontiguousarray(w2.transpose(1, 0, 2)), [0])          # (64 y1-channels, 64 padded rows)
-            self.conv_op("w_dnn.2.dgrad", [src], self.wadd("w_dnn.2.wd", w2d), None, 64, 64, F, F, F, 1, 0, 1, [0], [0],
-                         prg.EPI_LINEAR, dy1, 64)
+            w2d = pack_taps(np.ascontiguousarray(w2.transpose(1, 0, 2)), pw.taps)          # (64 y1-channels, 64 padded rows)
+            self.conv_op("w_dnn.2.dgrad", [src], self.wadd("w_dnn.2.wd", w2d), None, pw, N=64, epi=prg.EPI_LINEAR, dst=dy1)
             self.emit = self.fwd
             dpre = self.alloc(rows * 64)
             self.bwd.append(GenOp(OP_RELU_BWD, [dy1, y1.ref, dpre], list(_split64(rows * 64)), name="w_dnn.relu_bwd"))
-            self.wgrad_op("w_dnn.0.wgrad", dpre, 64, F, [h2], F, 1, 0, 1, [0], [0], w1img, dbias=self.gadd([b1img]))
-            w1d = self.pack_taps_idx(np.ascontiguousarray(w1.transpose(1, 0, 2)), [0])
-            self.dgrad("w_dnn.0.dgrad", h2, dpre, 64, F, [(self.wadd("w_dnn.0.wd", w1d), F, 1, 0, 1, [0], [0])])
+            self.wgrad_op("w_dnn.0.wgrad", dpre, [h2], pw, w1img, N=64, dbias=self.gadd([b1img]))
+            w1d = pack_taps(np.ascontiguousarray(w1.transpose(1, 0, 2)), pw.taps)
+            self.dgrad("w_dnn.0.dgrad", h2, dpre, [(self.wadd("w_dnn.0.wd", w1d), pw)], N=64)
             for p, hin, h, gates, wcat in reversed(layers):
                 dg = self.alloc(rows * 256)
                 self.bwd.append(GenOp(OP_LSTM_BWD, [gates, self.grad_of(h), wcat, dg], [B, T, F, self.lstm_prec], name=p + ".bwd"))
                 self.flops_bwd += 2 * rows * 256 * 64
-                self.wgrad_op(p + ".wgrad_ih", dg, 256, F, [hin], F, 1, 0, 1, [0], [0], self.idx(f"{p}.weight_ih_l0"),
+                self.wgrad_op(p + ".wgrad_ih", dg, [hin], pw, self.idx(f"{p}.weight_ih_l0"), N=256,
                               dbias=self.gadd([self.idx(f"{p}.bias_ih_l0"), self.idx(f"{p}.bias_hh_l0")]))
-                self.wgrad_op(p + ".wgrad_hh", dg, 256, F, [h], F, 1, 0, 1, [-1], [0], self.idx(f"{p}.weight_hh_l0"))
-                wih_d = self.pack_taps_idx(np.ascontiguousarray(self.idx(f"{p}.weight_ih_l0").T)[:, :, None], [0])   # (64, 256)
-                self.dgrad(p + ".dgrad", hin, dg, 256, F, [(self.wadd(p + ".wd", wih_d), F, 1, 0, 1, [0], [0])])
+                # (the recurrent product reads the hidden state of the previous frame)
+                self.wgrad_op(p + ".wgrad_hh", dg, [h], Geometry.pointwise(F, dt=-1), self.idx(f"{p}.weight_hh_l0"), N=256)
+                wih_d = pack_taps(np.ascontiguousarray(self.idx(f"{p}.weight_ih_l0").T)[:, :, None], pw.taps)   # (64, 256)
+                self.dgrad(p + ".dgrad", hin, dg, [(self.wadd(p + ".wd", wih_d), pw)], N=256)
             de = self.alloc(rows * 64)
             self.bwd.append(GenOp(OP_LN_BWD, [self.grad_of(x_ln), e.ref, mr_ln, lg, de, self.gvec("bf_map.norm.weight"),
                                               self.gvec("bf_map.norm.bias")], list(_split64(rows)), name="bf_map.norm.bwd"))

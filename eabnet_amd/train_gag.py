@@ -23,7 +23,7 @@ import numpy as np
 
 from . import program as prg
 from . import train as tr
-from .program import Ref, glu_row_order
+from .program import Geometry, Ref, glu_row_order, pack_taps, tcm_taps
 from .spec import GagConfig, gag_param_specs
 from .train import GenOp, TVar, TrainLowering, TrainProgram, _split64
 
@@ -52,23 +52,24 @@ class GagTrainLowering(TrainLowering):
         wk[:, D:D + 2 * Fq] = w[:, cols_pre]
         order = glu_row_order(2 * D)
         wk = wk[order]
-        wimg = self.pack_taps_idx(wk[:, :, None], [0])
+        one = Geometry.pointwise(1)
+        wimg = pack_taps(wk[:, :, None], one.taps)
         bimg = np.concatenate([self.idx(f"{pfx}.in_conv_main.bias"), self.idx(f"{pfx}.in_conv_gate.0.bias")])[order]
         out = self.act(1, D)
         rows = self.B * self.T
         dump = self.alloc(rows * 2 * D)
-        self.conv_op(f"{pfx}.in_conv", [feat, pre], self.wadd(f"{pfx}.in_conv.w", wimg), self.wadd(f"{pfx}.in_conv.b", bimg), 2 * D,
-                     wimg.shape[1], 1, 1, 1, 1, 0, 1, [0], [0], prg.EPI_GLU, out.ref, D, bm=64, glu_dump=dump)
+        self.conv_op(f"{pfx}.in_conv", [feat, pre], self.wadd(f"{pfx}.in_conv.w", wimg), self.wadd(f"{pfx}.in_conv.b", bimg), one,
+                     N=2 * D, epi=prg.EPI_GLU, dst=out.ref, bm=64, glu_dump=dump)
 
         def back():
             dz = self.alloc(rows * 2 * D)
             self.bwd.append(GenOp(tr.OP_GLU_BWD, [self.grad_of(out), dump, dz], list(_split64(rows)) + [2 * D], name=f"{pfx}.in_conv.glu_bwd"))
-            self.wgrad_op(f"{pfx}.in_conv.wgrad", dz, 2 * D, 1, [feat, pre], 1, 1, 0, 1, [0], [0], wimg, dbias=self.gadd([bimg]))
+            self.wgrad_op(f"{pfx}.in_conv.wgrad", dz, [feat, pre], one, wimg, N=2 * D, dbias=self.gadd([bimg]))
             c_lo = 0
             for s in (feat, pre):
                 if s.needs_grad:
-                    img = self.pack_taps_idx(np.ascontiguousarray(wk[:, c_lo:c_lo + s.C].T)[:, :, None], [0])      # (C_s, 2D, 1)
-                    self.dgrad(f"{pfx}.in_conv.dgrad{c_lo}", s, dz, 2 * D, 1, [(self.wadd(f"{pfx}.in_conv.wd{c_lo}", img), 1, 1, 0, 1, [0], [0])])
+                    img = pack_taps(np.ascontiguousarray(wk[:, c_lo:c_lo + s.C].T)[:, :, None], one.taps)      # (C_s, 2D, 1)
+                    self.dgrad(f"{pfx}.in_conv.dgrad{c_lo}", s, dz, [(self.wadd(f"{pfx}.in_conv.wd{c_lo}", img), one)], N=2 * D)
                 c_lo += s.C
         self.tape.append(back)
         return out
@@ -77,17 +78,14 @@ class GagTrainLowering(TrainLowering):
         """GaGNet's single-branch SqueezedTCM (GaGNet.py:303-327): in_conv -> PReLU/norm/dilated conv -> PReLU/norm/out_conv
         + residual"""
         cfg = self.cfg
-        kd = cfg.kd1
-        y, back_in = self.conv1d(f"{pre}.in_conv", x, self.idx(f"{pre}.in_conv.weight"), [0], None, prg.EPI_LINEAR, wname=f"{pre}.in_conv")
+        one, gd = Geometry.pointwise(1), Geometry.temporal(tcm_taps(cfg.kd1, dilation, cfg.is_causal))
+        y, back_in = self.conv1d(f"{pre}.in_conv", x, self.idx(f"{pre}.in_conv.weight"), None, one, epi=prg.EPI_LINEAR, wname=f"{pre}.in_conv")
         self.tape.append(lambda: back_in(self.grad_of(y)))
         yd = self.in1d(f"{pre}.d", y, f"{pre}.d_conv.1", f"{pre}.d_conv.0")
-        span = (kd - 1) * dilation
-        lead = span if cfg.is_causal else span // 2
-        dts = [j * dilation - lead for j in range(kd)]
-        z, back_d = self.conv1d(f"{pre}.d_conv", yd, self.idx(f"{pre}.d_conv.3.weight"), dts, None, prg.EPI_LINEAR, wname=f"{pre}.d_conv")
+        z, back_d = self.conv1d(f"{pre}.d_conv", yd, self.idx(f"{pre}.d_conv.3.weight"), None, gd, epi=prg.EPI_LINEAR, wname=f"{pre}.d_conv")
         self.tape.append(lambda: back_d(self.grad_of(z)))
         zo = self.in1d(f"{pre}.out", z, f"{pre}.out_conv.1", f"{pre}.out_conv.0")
-        out, back_out = self.conv1d(f"{pre}.out_conv", zo, self.idx(f"{pre}.out_conv.2.weight"), [0], None, prg.EPI_ADD, aux=x,
+        out, back_out = self.conv1d(f"{pre}.out_conv", zo, self.idx(f"{pre}.out_conv.2.weight"), None, one, epi=prg.EPI_ADD, aux=x,
                                     wname=f"{pre}.out_conv")
 
         def back():
@@ -109,7 +107,7 @@ class GagTrainLowering(TrainLowering):
         w = np.full((LIN_LD, D, 1), -1, dtype=np.int64)
         b = np.full(LIN_LD, -1, dtype=np.int64)
         w[:Fq], b[:Fq] = self.idx(f"{key}.weight"), self.idx(f"{key}.bias")
-        return self.conv1d(key, x, w, [0], b, prg.EPI_LINEAR, wname=key)
+        return self.conv1d(key, x, w, b, Geometry.pointwise(1), epi=prg.EPI_LINEAR, wname=key)
 
     # ---- whole network -----------------------------------------------------------------------------------------
     def build(self) -> TrainProgram:
