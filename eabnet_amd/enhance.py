@@ -6,11 +6,16 @@ program and of the back end serves up to ``max_batch`` of them.
 with per-utterance lengths (``stft_compress(lengths=)``, ``forward(lengths=)``, ``istft(lengths=)``)."""
 from __future__ import annotations
 
+import importlib
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
 from . import model as _m
+
+_rs = importlib.import_module(__package__ + ".resample")     # (the package's attribute `resample` is the function)
+
+MODEL_RATE = 16000                            # the sample rate of the networks (enhance.py:35-37 resamples every file to it)
 
 
 class Batch(NamedTuple):
@@ -85,11 +90,20 @@ class Enhancer:
     frames would read the padding): they -- and files above the largest cap -- run one file at a time on the exact-shape
     path, with the same result and no speed-up.
 
+    ``sample_rate``: the rate of the waves handed in (the reference resamples every file to 16 kHz first, enhance.py:35-37).
+    Other than 16000, the waves are packed at their own rate and ONE launch of the resampling kernel per batch
+    (``eabnet_amd.resample``, with the files' lengths) writes the 16 kHz (B, M, L) buffer the front end reads; the plan runs on
+    the frame counts of the resampled lengths, and every wave equals, bit for bit, what the 16 kHz enhancer returns for
+    ``resample(wave, sample_rate, 16000)``.  ``mic_order``: the microphones of a file in the model's order (a permutation or a
+    selection, enhance.py:41-42); the resampling kernel applies it as its row map, the packing does where the rate stays.
+    ``output_rate``: None returns 16 kHz waves (enhance.py:63), an int or "input" resamples each batch's enhanced waves, with
+    their lengths, before they are sliced out.
+
     ``last_plan`` describes the last call: its batches (files, cap, batch size, dummies, frames), the dummy count, and the
     valid frames against the frames padded up to each batch's longest member and up to its cap."""
 
     def __init__(self, model, max_batch: int = 16, fft_num: int = 320, hop: int = 160, window: Optional[torch.Tensor] = None,
-                 length_buckets="auto"):
+                 length_buckets="auto", sample_rate: int = MODEL_RATE, mic_order=None, output_rate=None):
         if isinstance(model, _m.EaBNetWithPostNet):
             self.nets = (model.eabnet, model.postnet)
         elif isinstance(model, _m.EaBNet):
@@ -105,6 +119,18 @@ class Enhancer:
         self.last_plan: Optional[dict] = None
         self._too_big: set = set()          # (cap, batch size, F, precisions, budgets) whose arena exceeds the budget
         self.phase_hook = None              # tools: called with "pack" / "stft" / "model" / "istft" / "slice" after each phase
+        self.sample_rate = int(sample_rate)
+        self._ratio = _rs._ratio(sample_rate, MODEL_RATE)                 # (o, n): o input samples per n model samples
+        if self._ratio[0] != self._ratio[1]:
+            _rs._check_span(*self._ratio, _rs.filter_bank(sample_rate, MODEL_RATE)[4], sample_rate, MODEL_RATE)
+        self.mic_order = _rs.check_mic_order(mic_order, 1 << 30)           # (against the files' microphone count: in the call)
+        self.output_rate = MODEL_RATE if output_rate is None else self.sample_rate if output_rate == "input" else output_rate
+        if isinstance(self.output_rate, (str, bool)) or int(self.output_rate) != self.output_rate or self.output_rate < 1:
+            raise ValueError(f'output_rate must be None, "input" or a sample rate, got {output_rate!r}')
+        self.output_rate = int(self.output_rate)
+        if self.output_rate != MODEL_RATE:
+            ro, rn = _rs._ratio(MODEL_RATE, self.output_rate)
+            _rs._check_span(ro, rn, _rs.filter_bank(MODEL_RATE, self.output_rate)[4], MODEL_RATE, self.output_rate)
 
     def _tick(self, phase: str) -> None:
         if self.phase_hook is not None:
@@ -137,9 +163,11 @@ class Enhancer:
         return plan
 
     # -- one batch -------------------------------------------------------------------
-    def _pack(self, waves, M: int, B: int, L: int, device: torch.device, role: int = 0):
+    def _pack(self, waves, M: int, B: int, L: int, device: torch.device, role: int = 0, order=None):
         """the waves of a batch as one zero-padded (B, M, L) device buffer (+ the staging ring's event, or None); role: the
-        staging ring (``_HostStager.upload``) -- a second input of the batch keeps its own"""
+        staging ring (``_HostStager.upload``) -- a second input of the batch keeps its own; order: the microphones to take"""
+        if order is not None:
+            waves = [w[list(order)] for w in waves]
         if all(w.is_cuda for w in waves):
             buf = torch.zeros((B, M, L), dtype=torch.float32, device=device)
             ev = None
@@ -164,27 +192,60 @@ class Enhancer:
         the model's final estimate (B, 2, T, F), the padded waves (B, hop * (T - 1)), and the sample and frame counts of all B
         slots, dummies included (varlen False: one file on the exact-shape path)"""
 
+    def _to_model_rate(self, waves, M_file: int, B: int, L: int, lens_in, device: torch.device, role: int = 0, order=None):
+        """waves at ``sample_rate`` -> the (B, M, L) buffer at 16 kHz: packed at their own rate into (B, M_file, L o // n) and
+        resampled by one launch with their lengths (None: one file, its full row) and ``order`` as the row map; the rows past
+        ceil(n len / o) samples are zeros.  Returns (buffer, staging event or None); the event is recorded after the launch"""
+        o, n = self._ratio
+        raw, ev = self._pack(waves, M_file, B, max(L * o // n, max(w.shape[1] for w in waves)), device, role)
+        buf = _rs._resample_rows(raw, self.sample_rate, MODEL_RATE, lens_in, order, L)
+        if ev is not None:
+            ev.record(torch.cuda.current_stream(device))
+        return buf, ev
+
+    def _output(self, wav: torch.Tensor, lens) -> torch.Tensor:
+        """the enhanced (B, W) waves of a batch at ``output_rate`` (lens: their sample counts, or None for full rows)"""
+        if self.output_rate == MODEL_RATE:
+            return wav
+        return _rs.resample(wav, MODEL_RATE, self.output_rate, lengths=lens)
+
+    def _out_len(self, samples: int) -> int:
+        return _rs.resampled_length(samples, MODEL_RATE, self.output_rate)
+
     def _run(self, batch: Batch, waves, frames, device: torch.device, varlen: bool) -> List[torch.Tensor]:
         fft, hop = self.fft_num, self.hop
         mine = [waves[i] for i in batch.indices]
-        M = mine[0].shape[0]
+        M_file = mine[0].shape[0]
+        M = M_file if self.mic_order is None else len(self.mic_order)
+        o, n = self._ratio
+        convert = o != n
         if not varlen or batch.cap is None:                       # one file, exact-shape path
-            buf, ev = self._pack(mine, M, 1, mine[0].shape[1], device)
+            if convert:
+                buf, ev = self._to_model_rate(mine, M_file, 1, _rs.resampled_length(mine[0].shape[1], o, n), None, device,
+                                              order=self.mic_order)
+            else:
+                buf, ev = self._pack(mine, M, 1, mine[0].shape[1], device, order=self.mic_order)
             spec = _m.stft_compress(buf, fft, hop, self.window)
             if ev is not None:
                 ev.record(torch.cuda.current_stream(device))
             est = self._model(spec, None)
             wav = _m.istft(est, fft, hop, self.window)
             self._batch_done(batch, buf, ev, est, wav, [buf.shape[2]], [est.shape[2]], False, device)
-            return [wav[0]]
+            return [self._output(wav, None)[0]]
         B, T_max = batch.batch_size, frames[batch.indices[0]]
         # host waves: one buffer shape per (cap, batch size), so the staging ring is allocated once; device waves: no longer
         # than the longest file needs
         host = not all(w.is_cuda for w in mine)
-        L = _padded_len(max(w.shape[1] for w in mine), batch.cap if host else T_max, hop)
-        samples = [w.shape[1] for w in mine] + [fft // 2 + 1] * batch.dummies
-        counts = [1 + n // hop for n in samples]
-        buf, ev = self._pack(mine, M, B, L, device)
+        # a dummy utterance: the fewest input samples that resample to more than fft_num/2
+        dummy_in = -(-(fft // 2 + 1) * o // n)
+        lens_in = [w.shape[1] for w in mine] + [dummy_in] * batch.dummies
+        samples = [_rs.resampled_length(v, o, n) for v in lens_in]
+        L = _padded_len(max(samples), batch.cap if host else T_max, hop)
+        counts = [1 + v // hop for v in samples]
+        if convert:
+            buf, ev = self._to_model_rate(mine, M_file, B, L, lens_in, device, order=self.mic_order)
+        else:
+            buf, ev = self._pack(mine, M, B, L, device, order=self.mic_order)
         self._tick("pack")
         spec = _m.stft_compress(buf, fft, hop, self.window, lengths=samples)
         if ev is not None:
@@ -194,7 +255,8 @@ class Enhancer:
         self._tick("model")
         wav = _m.istft(est, fft, hop, self.window, lengths=counts)
         self._tick("istft")
-        out = [wav[k, :hop * (counts[k] - 1)].clone() for k in range(len(mine))]
+        res = self._output(wav, [hop * (c - 1) for c in counts])
+        out = [res[k, :self._out_len(hop * (counts[k] - 1))].clone() for k in range(len(mine))]
         self._tick("slice")
         self._batch_done(batch, buf, ev, est, wav, samples, counts, True, device)
         return out
@@ -208,15 +270,22 @@ class Enhancer:
             self.last_plan = dict(batches=[], dummies=0, valid_frames=0, padded_frames=0, cap_frames=0)
             return []
         M = waves[0].shape[0] if waves[0].ndim == 2 else -1
+        o, n = self._ratio
         for w in waves:
-            if w.ndim != 2 or w.shape[0] != M or w.shape[1] <= self.fft_num // 2:
-                raise ValueError(f"waves must be (M, L) tensors of one microphone count with L > fft_num/2 = {self.fft_num // 2}, "
-                                 f"got {tuple(w.shape)}")
+            if w.ndim != 2 or w.shape[0] != M or _rs.resampled_length(w.shape[1], o, n) <= self.fft_num // 2:
+                raise ValueError(f"waves must be (M, L) tensors of one microphone count with L > fft_num/2 = {self.fft_num // 2}"
+                                 f"{'' if o == n else ' at 16 kHz'}, got {tuple(w.shape)}")
+        if self.mic_order is not None:
+            _rs.check_mic_order(self.mic_order, M)
+        M_model = self.nets[0].cfg.M
+        if (M if self.mic_order is None else len(self.mic_order)) != M_model:
+            raise ValueError(f"the model takes {M_model} microphones, the files hold {M}"
+                             + ("" if self.mic_order is None else f" and mic_order selects {len(self.mic_order)}"))
         _m._lib.load()
         device = next(self.model.parameters()).device
         if device.type != "cuda":
             raise _m._lib.EabError("Enhancer runs on MI355X only: move the model to 'cuda'. There is no CPU fallback by design.")
-        frames = [1 + w.shape[1] // self.hop for w in waves]
+        frames = [1 + _rs.resampled_length(w.shape[1], o, n) // self.hop for w in waves]
         F = self.fft_num // 2 + 1
         varlen = all(n.cfg.is_causal for n in self.nets)
         own = self.model.length_buckets is None

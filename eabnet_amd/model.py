@@ -953,12 +953,28 @@ class StreamingEnhancer:
     k and k+1, so the enhanced wave trails the input by two hops (20 ms at 16 kHz) plus the compute time of a
     step.  Front and back end are the offline kernels on short windows (a frame / segment is computed
     identically wherever its window starts), so the streamed wave is bit-identical to the offline
-    wave -> prepare_data -> model -> istft chain."""
+    wave -> prepare_data -> model -> istft chain.
+
+    ``sample_rate`` (None: ``sr``): the rate of the pushed samples.  ``push`` then takes chunk*hop*sample_rate/sr samples per
+    call; a ``StreamResampler`` turns them into ``sr`` samples (bit for bit those of the offline ``resample``), which queue up
+    until a whole chunk*hop block is there for the push logic above.  The output (at ``sr``) trails the input by the filter's
+    half-width more -- 19 samples at 48 kHz, 0.4 ms -- so the first call returns one block less and ``last=True`` returns the
+    rest.  ``mic_order``: the microphones of the pushed samples in the model's order."""
 
     def __init__(self, model, B: int, seconds: float, chunk: int = 1, sr: int = 16000, fft_num: int = 320, hop: int = 160,
-                 endless: bool = False):
+                 endless: bool = False, sample_rate: Optional[int] = None, mic_order=None):
         """seconds: the longest stream; with endless=True the resident window of a stream of any length (see
         EaBNetStream: it must hold twice the network's history plus a chunk)."""
+        import importlib
+        _rs = importlib.import_module(__package__ + ".resample")     # (the package's attribute `resample` is the function)
+        self._rs, self._push_in = None, chunk * hop
+        self._order = None if mic_order is None else list(_rs.check_mic_order(mic_order, 1 << 30))
+        if sample_rate is not None and int(sample_rate) != int(sr):
+            o, n = _rs._ratio(sample_rate, sr)
+            if (chunk * hop * o) % n:
+                raise ValueError(f"push takes chunk*hop*{o}/{n} = {chunk * hop * o / n} samples at {sample_rate} Hz per call: "
+                                 f"not a whole number; choose a chunk that makes it one")
+            self._rs, self._push_in = _rs.StreamResampler(sample_rate, sr), chunk * hop * o // n
         self.model, self.B, self.chunk, self.fft, self.hop = model, B, chunk, fft_num, hop
         self.T_max = 1 + int(seconds * sr) // hop
         self.stream = model.stream_begin(B, self.T_max, chunk, endless=endless)
@@ -971,10 +987,36 @@ class StreamingEnhancer:
         self._hold = None          # samples of a first push too short to form frame 0
         self._frames = 0           # frames handed to the model so far
         self._spec_prev = None     # last estimate frame, for the overlap-add with the next one
+        self._fifo = None          # resampled samples (B, M, < chunk*hop) waiting for a whole block
+        if self._rs is not None:
+            self._rs.reset()
 
     def push(self, samples: torch.Tensor, last: bool = False) -> torch.Tensor:
         """samples (B, M, n*hop), n == chunk (any 0 <= n <= chunk with last=True).  Returns (B, k*hop)
-        enhanced samples, k = frames that became final in this call."""
+        enhanced samples, k = frames that became final in this call.  With ``sample_rate``: (B, M, chunk*hop*sample_rate/sr)
+        samples per call (fewer with last=True, as long as the whole stream comes to whole hops at ``sr``)."""
+        if self._order is not None:
+            samples = samples[:, self._order]
+        if self._rs is None:
+            return self._push(samples, last)
+        if samples.shape[2] > self._push_in or (samples.shape[2] != self._push_in and not last):
+            raise ValueError(f"push takes {self._push_in} samples per call (fewer only with last=True)")
+        new = self._rs.push(samples, last)
+        fifo = new if self._fifo is None else torch.cat((self._fifo, new), dim=2)
+        blk, outs = self.chunk * self.hop, []
+        while fifo.shape[2] >= blk and not (last and fifo.shape[2] == blk):
+            outs.append(self._push(fifo[:, :, :blk], False))
+            fifo = fifo[:, :, blk:]
+        if last:
+            outs.append(self._push(fifo, True))               # the rest: at most one block
+            fifo = None
+        self._fifo = fifo
+        outs = [y for y in outs if y.shape[1]]
+        if not outs:
+            return samples.new_zeros((samples.shape[0], 0))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
+
+    def _push(self, samples: torch.Tensor, last: bool) -> torch.Tensor:
         B, M, L = samples.shape
         if L % self.hop or L // self.hop > self.chunk or (L // self.hop != self.chunk and not last):
             raise ValueError(f"push takes chunk*hop = {self.chunk * self.hop} samples per call (fewer only with last=True)")

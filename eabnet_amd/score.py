@@ -126,12 +126,14 @@ class Scorer(Enhancer):
     model's final estimate against it (``com_mag_mse_loss_per_utterance``) and the energy ratios of (enhanced wave, clean,
     noisy[ref_mic]) with the lengths (hop * (T_b - 1), L_b, L_b) (``energy_ratios``).  The rows go into one (N, 5) float64
     device table at the files' input positions, dummy slots dropped; the table is copied to the host once, at the end of the
-    call -- nothing synchronises per file or per batch.  Non-causal models and files above the largest cap run one file at a
+    call -- nothing synchronises per file or per batch.  ``sample_rate`` / ``mic_order`` as in ``Enhancer``: the noisy AND the clean
+    waves are resampled to 16 kHz on the device (test.py:65-68), the clean ones by a second launch with the same bank, and the
+    scores are those of the 16 kHz signals; ``ref_mic`` counts in the model's microphone order.  Non-causal models and files above the largest cap run one file at a
     time through the same kernels at B = 1.  ``summary(scores)``: {metric: (mean, std)} with NaNs dropped (metrics.mean_std)."""
 
     def __init__(self, model, max_batch: int = 16, fft_num: int = 320, hop: int = 160, window: Optional[torch.Tensor] = None,
-                 length_buckets="auto", ref_mic: int = 0):
-        super().__init__(model, max_batch, fft_num, hop, window, length_buckets)
+                 length_buckets="auto", ref_mic: int = 0, sample_rate: int = 16000, mic_order=None):
+        super().__init__(model, max_batch, fft_num, hop, window, length_buckets, sample_rate=sample_rate, mic_order=mic_order)
         if int(ref_mic) != ref_mic or ref_mic < 0:
             raise ValueError(f"ref_mic must be a microphone index, got {ref_mic}")
         self.ref_mic = int(ref_mic)
@@ -142,7 +144,15 @@ class Scorer(Enhancer):
     def _batch_done(self, batch: Batch, noisy, ev, est, wav, samples, counts, varlen: bool, device) -> None:
         fft, hop = self.fft_num, self.hop
         B, M, L = noisy.shape
-        cbuf, cev = self._pack([self._clean[i] for i in batch.indices], 1, B, L, device, role=1)
+        clean = [self._clean[i] for i in batch.indices]
+        if self._ratio[0] != self._ratio[1]:                  # the clean waves through the same bank, in their own staging role
+            lens_in = None
+            if varlen:
+                dummy_in = -(-(fft // 2 + 1) * self._ratio[0] // self._ratio[1])
+                lens_in = [c.shape[1] for c in clean] + [dummy_in] * batch.dummies
+            cbuf, cev = self._to_model_rate(clean, 1, B, L, lens_in, device, role=1)
+        else:
+            cbuf, cev = self._pack(clean, 1, B, L, device, role=1)
         self._tick("pack_clean")
         label = _m.stft_compress(cbuf, fft, hop, self.window, 1, lengths=samples if varlen else None)
         self._tick("stft_clean")
@@ -169,8 +179,10 @@ class Scorer(Enhancer):
                 raise ValueError(f"Scorer: clean waves must be (L,) or (1, L) tensors, file {k} is {tuple(c.shape)}")
             if x.ndim != 2 or x.shape[1] != c.shape[1]:
                 raise ValueError(f"Scorer: file {k} has {tuple(x.shape)} noisy but {c.shape[1]} clean samples; the lengths must agree")
-            if self.ref_mic >= x.shape[0]:
-                raise ValueError(f"Scorer: ref_mic = {self.ref_mic} but file {k} has {x.shape[0]} microphones")
+            mics = x.shape[0] if self.mic_order is None else len(self.mic_order)
+            if self.ref_mic >= mics:
+                raise ValueError(f"Scorer: ref_mic = {self.ref_mic} but file {k} has {mics} microphones"
+                                 + ("" if self.mic_order is None else " after mic_order"))
         if self.model.training:
             raise RuntimeError("Scorer: call model.eval() first")
         N = len(noisy)

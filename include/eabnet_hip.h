@@ -197,6 +197,30 @@ int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* label, const i
                                   int F, double* partial, int partial_spans, double* loss, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Sample-rate conversion of the rows of a padded batch (csrc/resample.hip).  Replaces, one file at a time on the host,
+ * torchaudio.transforms.Resample(sr, 16000) of enhance.py:35-37 and test.py:65-68, and the microphone index_select of
+ * enhance.py:41-42.  Only an entry point is added: EAB_ABI_VERSION stays 10.
+ *
+ * For rates orig -> new with g = gcd: o = orig/g, n = new/g.  Output sample i = q*n + p (phase p in [0, n)) of a row is
+ *     y[i] = sum_{k < K} tab[p][k] * x[q*o + first[p] + k]        (fp32, ascending k, one fmaf per tap)
+ *   tab   DEVICE float [n][K], first DEVICE int32 [n]: the polyphase bank of the windowed-sinc prototype
+ *         (eabnet_amd.resample.filter_bank); first[] is nondecreasing and first[n-1] - first[0] <= o;  K*n <= 16384
+ *   x     rows (utterance, microphone) of x_cols floats, row r of the OUTPUT reads input row row_map[r] (DEVICE int32 [rows];
+ *         NULL: row r) at x + row*x_row_stride; y [rows] rows of n_out floats at y + r*y_row_stride
+ *   in_lens  NULL or DEVICE int32 [ceil(rows / rows_per_utt)]: valid samples of utterance u = r / rows_per_utt, clamped to
+ *         [0, x_cols]; samples at and past it count as zero and are never read, and the outputs at and past
+ *         ceil(n*len/o) (as absolute positions) are written as zeros up to n_out
+ *   in_origin, out_origin: absolute sample indices of x[., 0] and y[., 0] (0 for a whole signal; a stream passes the
+ *         position of its carry buffer); a sample whose absolute index is < 0 or >= valid_hi (valid_hi < 0: in_origin +
+ *         x_cols), or that lies before x[., 0], is zero
+ * One summation order per output sample: a row has the same bits alone, in any batch, at any tile position and in a stream.
+ * EAB_EINVAL also for a decimation so steep that the input span of 256 outputs exceeds 12288 floats.
+ * ------------------------------------------------------------------------ */
+int eab_resample_f32(const float* x, long long x_row_stride, int x_cols, const int32_t* row_map, const int32_t* in_lens, int rows,
+                     int rows_per_utt, float* y, long long y_row_stride, int n_out, const float* tab, const int32_t* first, int o,
+                     int n, int K, long long in_origin, long long out_origin, long long valid_hi, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * K13  complex filter-and-sum, stand-alone.   Replaces EaBNet.py:114-117.
  *   w, x [B][T][F][M][2] -> y [B][2][T][F];  Y = sum_m W_m * X_m (no conjugate)
  * ------------------------------------------------------------------------ */
