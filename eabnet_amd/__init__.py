@@ -12,11 +12,11 @@ from .model import (EaBNet, GaGNet, EaBNetWithPostNet, make_gag_net, make_eabnet
                     StreamingEnhancer, Pipeline, prepare_data, stft_compress, istft, filter_and_sum, numParams, com_mag_mse_loss,
                     stagewise_com_mag_mse_loss, eabnet_with_postnet_loss)
 from .enhance import Enhancer, plan_batches  # noqa: F401
-from .score import Scorer, energy_ratios, com_mag_mse_loss_per_utterance  # noqa: F401
+from .score import Scorer, energy_ratios, com_mag_mse_loss_per_utterance, intelligibility, stoi  # noqa: F401
 from .resample import resample, resampled_length, filter_bank, StreamResampler  # noqa: F401
 
 __all__ = ["EaBNet", "GaGNet", "EaBNetWithPostNet", "make_gag_net", "make_eabnet_with_postnet", "StreamingEnhancer", "Pipeline", "Enhancer", "plan_batches", "Scorer", "energy_ratios",
-           "com_mag_mse_loss_per_utterance", "resample", "resampled_length", "filter_bank", "StreamResampler",
+           "com_mag_mse_loss_per_utterance", "intelligibility", "stoi", "resample", "resampled_length", "filter_bank", "StreamResampler",
            "prepare_data",
            "stft_compress", "istft", "filter_and_sum", "numParams", "com_mag_mse_loss", "stagewise_com_mag_mse_loss",
            "eabnet_with_postnet_loss",

@@ -101,6 +101,10 @@ _SIGS = {
     "eab_energy_ratios_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]),
     "eab_com_mag_mse_loss_lens_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "eab_stoi_frame_capacity": (C.c_int, [C.c_int]),
+    "eab_stoi_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "eab_stoi_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
+                     + [C.c_void_p] * 5),
     "eab_resample_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p]),

@@ -4,7 +4,11 @@
 
 ``energy_ratios`` and ``com_mag_mse_loss_per_utterance`` are the two kernels of csrc/score.hip behind tensor arguments;
 ``Scorer`` is an ``Enhancer`` that also packs the clean waves, takes their label spectrum and fills one (N, 5) float64 device
-table -- si_sdr, si_sir, si_sar, si_sdr_mix, loss per file -- which it copies to the host once per call."""
+table -- si_sdr, si_sir, si_sar, si_sdr_mix, loss per file -- which it copies to the host once per call.
+
+``intelligibility`` is csrc/stoi.hip behind tensor arguments: STOI and ESTOI per utterance at 10 kHz (the two remaining
+closed-form metrics of cal_single_metrics), ``stoi`` the same with the host library's argument order, and
+``Scorer(..., intelligibility=True)`` adds them as two more columns."""
 from __future__ import annotations
 
 import ctypes as C
@@ -15,10 +19,12 @@ import torch
 
 from . import _lib
 from . import model as _m
-from .enhance import Batch, Enhancer
+from .enhance import MODEL_RATE, Batch, Enhancer, _rs
 
 SPAN = 4096                                   # SCORE_SPAN of csrc/score.hip: samples (bins) per partial row
 METRICS = ("si_sdr", "si_sir", "si_sar", "si_sdr_mix", "loss")
+INTELLIGIBILITY_METRICS = ("stoi", "estoi")
+STOI_RATE = 10000                             # the rate of the definition: other rates are resampled to it first
 
 
 def _spans(n: int) -> int:
@@ -116,7 +122,105 @@ def com_mag_mse_loss_per_utterance(esti: torch.Tensor, label: torch.Tensor, fram
     return out
 
 
-class Scorer(Enhancer):
+def _stoi_rows(est: torch.Tensor, clean: torch.Tensor, cols: list, taps: bool):
+    """the five launches of csrc/stoi.hip on 10 kHz rows: (B, 2) float64 [stoi, estoi] (and the taps)"""
+    est, clean = _rows(est, "est"), _rows(clean, "clean")
+    if est.device != clean.device:
+        raise ValueError("est and clean must be on one device")
+    B = est.shape[0]
+    lib = _lib.load()
+    cap = max(est.shape[1], clean.shape[1])
+    FC, nbytes = lib.eab_stoi_frame_capacity(cap), lib.eab_stoi_workspace_bytes(B, cap)
+    if FC < 0 or nbytes < 0:
+        raise ValueError(f"intelligibility takes at most 65535 rows of at most 2^30 samples, got {B} rows of {cap}")
+    with torch.cuda.device(est.device):
+        if not any(isinstance(c, torch.Tensor) for c in cols):
+            lens = _m._device_lengths([v for row in zip(*cols) for v in row], est.device).view(B, 2)
+        else:
+            lens = torch.stack([_m._device_lengths(c, est.device) for c in cols], dim=1).contiguous()
+        work = torch.empty((nbytes,), dtype=torch.uint8, device=est.device)
+        out = torch.empty((B, 2), dtype=torch.float64, device=est.device)
+        tap = None
+        if taps:                              # (zeros: the kernels write the first K, K and K - 1 entries of a row only)
+            tap = {"K": torch.zeros((B,), dtype=torch.int32, device=est.device),
+                   "kept": torch.zeros((B, FC), dtype=torch.int32, device=est.device),
+                   "tob": torch.zeros((B, 2, 15, FC), dtype=torch.float32, device=est.device)}
+        args = []
+        for t in (est, clean):
+            args += [t.data_ptr(), t.stride(0) if B > 1 else t.shape[1], t.shape[1]]
+        ptrs = [tap[k].data_ptr() for k in ("K", "kept", "tob")] if taps else [None, None, None]
+        _lib.check(lib.eab_stoi_f32(*args, lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), *ptrs,
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_stoi_f32")
+    return (out, tap) if taps else out
+
+
+def intelligibility(est: torch.Tensor, clean: torch.Tensor, lengths=None, sample_rate: int = 16000, taps: bool = False):
+    """STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) of B utterances: (B, Le), (B, Ls) CUDA fp32 tensors -> a (B, 2)
+    float64 device tensor ``[stoi, estoi]``, the two intelligibility numbers of cal_single_metrics (reference test.py:126-153).
+    The definition of DESIGN.md §4.16 is the contract (frames of 256 at hop 128 under the inner points of a 258-point Hann
+    window, frames more than 40 dB below the loudest clean frame removed, 15 third-octave bands from 150 Hz, segments of 30
+    frames; fewer than 30 band frames give the sentinel 1e-5 for both); it follows the widely used Python implementation, but
+    equality with that library's output is NOT verified.
+
+    Rows may be strided views whose last dimension is contiguous and are read in place, as in ``energy_ratios``.  lengths: an
+    optional pair of (B,) sample counts for (est, clean), host or device; a signal counts as zero from its own length up to the
+    longer of the two (test.py:126-138) and is never read there.  sample_rate: 10000 skips the resampler; at any other rate
+    each signal goes through ``resample(sig, sample_rate, 10000, lengths=...)`` with its default bank and its OWN length, and
+    the shorter output is then zero-extended -- this differs from "pad, then resample" only in the filter's ringing past the
+    shorter signal's end.  A silent clean row gives (0, 0).  fp64 sums in a fixed order: a row has the same bits alone, in any
+    batch and in a second call.  taps=True (tests): ``(scores, {"K", "kept", "tob"})``, the kept-frame counts, the source
+    frame of every compacted frame and the (B, 2, 15, frames) band values of (clean, est)."""
+    for name, t in (("est", est), ("clean", clean)):
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be a (B, L) tensor, got {tuple(t.shape)}")
+    B = est.shape[0]
+    if clean.shape[0] != B:
+        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
+    widths = (est.shape[1], clean.shape[1])
+    if lengths is None:
+        lengths = [[w] * B for w in widths]
+    lengths = list(lengths)
+    if len(lengths) != 2:
+        raise ValueError(f"lengths must be a pair (est, clean) of (B,) counts, got {len(lengths)} members")
+    cols = [_m.check_lengths(l, B, w, lo=1, unit="the signal's row length", integral=True) for l, w in zip(lengths, widths)]
+    o, n = _rs._ratio(sample_rate, STOI_RATE)
+    if not (est.is_cuda and clean.is_cuda):
+        raise _lib.EabError("intelligibility needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+    if o != n:
+        est, clean = (_rs.resample(_rows(t, "sig"), sample_rate, STOI_RATE, lengths=c) for t, c in zip((est, clean), cols))
+        cols = [(c.to(torch.int64) * n + (o - 1)) // o if isinstance(c, torch.Tensor) else [-(-n * v // o) for v in c]
+                for c in cols]
+    return _stoi_rows(est, clean, cols, taps)
+
+
+def stoi(clean, est, fs_sig: int, extended: bool = False) -> float:
+    """``stoi(clean, est, fs_sig, extended)`` with the host library's argument order, as test.py calls it: 1-D tensors or arrays
+    -> a Python float, STOI or (``extended=True``) ESTOI by ``intelligibility`` (whose definition, not that library's output, is
+    the contract).  Host inputs are copied to the current device; the call synchronises."""
+    sig = []
+    for v in (est, clean):
+        t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+        if t.ndim != 1 or t.shape[0] < 1:
+            raise ValueError(f"stoi takes 1-D signals, got {tuple(t.shape)}")
+        sig.append(t)
+    if not torch.cuda.is_available():
+        raise _lib.EabError("stoi runs on MI355X only; there is no CPU fallback by design.")
+    device = next((t.device for t in sig if t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    e, c = (t.to(device=device, dtype=torch.float32)[None] for t in sig)
+    return float(intelligibility(e, c, sample_rate=fs_sig)[0, 1 if extended else 0])
+
+
+class _ScorerType(type):
+    """``Scorer(..., intelligibility=True)``: the switch is a keyword of the class call, not of ``__init__``, whose parameter list
+    is pinned together with the other tools' (tests/test_resample_ref.py::test_defaults_of_the_tools_are_unchanged)."""
+
+    def __call__(cls, *args, intelligibility: bool = False, **kw):
+        self = super().__call__(*args, **kw)
+        self.intelligibility = bool(intelligibility)
+        return self
+
+
+class Scorer(Enhancer, metaclass=_ScorerType):
     """``scores = Scorer(model)(noisy_waves, clean_waves)``: lists of (M, L_i) noisy and (L_i,) or (1, L_i) clean waves, host or
     device -> a dict of (N,) float64 numpy arrays ``si_sdr, si_sir, si_sar, si_sdr_mix, loss`` in input order
     (``return_waves=True``: ``(scores, waves)`` with exactly ``Enhancer``'s waves).
@@ -129,7 +233,14 @@ class Scorer(Enhancer):
     call -- nothing synchronises per file or per batch.  ``sample_rate`` / ``mic_order`` as in ``Enhancer``: the noisy AND the clean
     waves are resampled to 16 kHz on the device (test.py:65-68), the clean ones by a second launch with the same bank, and the
     scores are those of the 16 kHz signals; ``ref_mic`` counts in the model's microphone order.  Non-causal models and files above the largest cap run one file at a
-    time through the same kernels at B = 1.  ``summary(scores)``: {metric: (mean, std)} with NaNs dropped (metrics.mean_std)."""
+    time through the same kernels at B = 1.  ``summary(scores)``: {metric: (mean, std)} with NaNs dropped (metrics.mean_std).
+
+    ``intelligibility=True`` adds the keys ``stoi`` and ``estoi`` (a (N, 7) table): per batch, on the same stream, the enhanced
+    waves and the clean buffer are resampled from 16 kHz to 10 kHz and scored by ``intelligibility`` with the lengths
+    (hop * (T_b - 1), L_b).  The default changes nothing: not the keys, the table, the launches or the bits.  (The attribute
+    ``scorer.intelligibility`` may also be set between calls.)"""
+
+    intelligibility = False
 
     def __init__(self, model, max_batch: int = 16, fft_num: int = 320, hop: int = 160, window: Optional[torch.Tensor] = None,
                  length_buckets="auto", ref_mic: int = 0, sample_rate: int = 16000, mic_order=None):
@@ -158,6 +269,8 @@ class Scorer(Enhancer):
         self._tick("stft_clean")
         loss = com_mag_mse_loss_per_utterance(est, label, counts)
         ratios = energy_ratios(wav, cbuf[:, 0], noisy[:, self.ref_mic], lengths=([hop * (t - 1) for t in counts], samples, samples))
+        if self.intelligibility:              # (before the events below: it reads the staged clean waves too)
+            intel = intelligibility(wav, cbuf[:, 0], lengths=([hop * (t - 1) for t in counts], samples), sample_rate=MODEL_RATE)
         for e in (ev, cev):
             if e is not None:                 # the staged noisy and clean waves have no reader after this point
                 e.record(torch.cuda.current_stream(device))
@@ -165,8 +278,15 @@ class Scorer(Enhancer):
         rows = self._stage[self._filled:self._filled + n]
         rows[:, :4].copy_(ratios[:n])
         rows[:, 4].copy_(loss[:n])
+        if self.intelligibility:
+            rows[:, 5:7].copy_(intel[:n])
         self._filled += n
         self._tick("score")
+
+    @property
+    def metrics(self) -> Tuple[str, ...]:
+        """the keys of the scores, in the order of the table's columns"""
+        return METRICS + (INTELLIGIBILITY_METRICS if self.intelligibility else ())
 
     @torch.no_grad()
     def __call__(self, noisy_waves: Sequence[torch.Tensor], clean_waves: Sequence[torch.Tensor], return_waves: bool = False):
@@ -188,7 +308,7 @@ class Scorer(Enhancer):
         N = len(noisy)
         if N == 0:
             super().__call__([])
-            scores = {m: np.zeros(0) for m in METRICS}
+            scores = {m: np.zeros(0) for m in self.metrics}
             return (scores, []) if return_waves else scores
         device = next(self.model.parameters()).device
         if device.type != "cuda":
@@ -196,7 +316,7 @@ class Scorer(Enhancer):
         self._clean, self._filled = clean, 0
         try:
             with torch.cuda.device(device):
-                self._stage = torch.empty((N, 5), dtype=torch.float64, device=device)        # rows in plan order
+                self._stage = torch.empty((N, len(self.metrics)), dtype=torch.float64, device=device)        # rows in plan order
             waves = super().__call__(noisy)
             assert self._filled == N
             with torch.cuda.device(device):
@@ -206,7 +326,7 @@ class Scorer(Enhancer):
                 host = table.cpu().numpy()                                                   # the call's one device-to-host copy
         finally:
             self._clean, self._stage = [], None
-        scores = {m: np.ascontiguousarray(host[:, j]) for j, m in enumerate(METRICS)}
+        scores = {m: np.ascontiguousarray(host[:, j]) for j, m in enumerate(self.metrics)}
         return (scores, waves) if return_waves else scores
 
     @staticmethod

@@ -197,6 +197,29 @@ int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* label, const i
                                   int F, double* partial, int partial_spans, double* loss, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Intelligibility per utterance of a padded batch at 10 kHz (csrc/stoi.hip): STOI and ESTOI of cal_single_metrics
+ * (test.py:126-153), by the definition of DESIGN.md §4.16 (the definition is the contract; equality with a host STOI library
+ * is not verified).  Only entry points are added: EAB_ABI_VERSION stays 10.
+ *
+ *   est, clean: row b of a signal starts at base + b*stride (floats) and is read in place; at most `cap` floats of it
+ *   lens    DEVICE int32 [B][2]: samples of (est, clean) of utterance b, clamped to [0, cap]; a signal counts as zero from
+ *           its own length up to the longer of the two, and is never read there
+ *   work    device scratch of eab_stoi_workspace_bytes(B, max(est_cap, clean_cap)) bytes, 16-byte aligned
+ *   out     device double [B][2]: stoi, estoi; 1e-5 for both when fewer than 30 band frames remain
+ *   tap_K, tap_kept, tap_tob: NULL, or device arrays that receive (tests), with FC = eab_stoi_frame_capacity(max cap),
+ *           int32 [B] the kept-frame counts K, int32 [B][FC] the source frame of every compacted frame t < K, and
+ *           float [B][2][15][FC] the third-octave band values of (clean, est) for t < K - 1
+ * Five launches, no host synchronisation, no atomics; fp64 sums in one fixed order per utterance: an utterance has the same
+ * bits alone, in any batch and in a second call, whatever the strides and alignments.
+ * eab_stoi_frame_capacity: frames of a signal of `cap` samples (at least 1); -1 for cap outside [1, 2^30].
+ * ------------------------------------------------------------------------ */
+int eab_stoi_frame_capacity(int cap);
+long long eab_stoi_workspace_bytes(int B, int cap);
+int eab_stoi_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride, int clean_cap,
+                 const int32_t* lens, int B, void* work, long long work_bytes, double* out, int32_t* tap_K, int32_t* tap_kept,
+                 float* tap_tob, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * Sample-rate conversion of the rows of a padded batch (csrc/resample.hip).  Replaces, one file at a time on the host,
  * torchaudio.transforms.Resample(sr, 16000) of enhance.py:35-37 and test.py:65-68, and the microphone index_select of
  * enhance.py:41-42.  Only an entry point is added: EAB_ABI_VERSION stays 10.
