@@ -27,14 +27,10 @@
 // fp32-in MFMA is exact fp32 (fmaf chain), 64 FLOP/clk/SIMD: one MFMA occupies
 // its SIMD for 64 cycles while needing one A and one B VGPR, so LDS and staging
 // traffic are far below their limits: roofline "mfma", fp32 dense 157.3 TFLOP/s.
-#include "common.h"
+#include "device.h"
 #include <type_traits>
 
 #define CG_THREADS 256
-#define CG_OOB 0x80000000u   // > any legal byte offset inside one batch element (host checks < 2^31)
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #define CG_PLAIN 0
 #define CG_GLU 1     // value/gate columns of ONE GEMM (GateConv2d / GateConvTranspose2d)
@@ -61,23 +57,8 @@ struct CgSmem {
     int last;                    // fused finalisation: this workgroup wrote the last partial of its batch element
 };
 
-template <int XF>
-__device__ __forceinline__ f32x4 cg_xform(f32x4 v, f32x4 sh01, f32x4 sh23, f32x4 sl) {
-    // sh01 = (scale0, shift0, scale1, shift1), sh23 likewise for channels 2,3
-    const float sc[4] = {sh01[0], sh01[2], sh23[0], sh23[2]};
-    const float sf[4] = {sh01[1], sh01[3], sh23[1], sh23[3]};
-    f32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (XF == EAB_XF_NORM_PRELU)
-            r[j] = eab_prelu(fmaf(v[j], sc[j], sf[j]), sl[j]);
-        else
-            r[j] = fmaf(eab_prelu(v[j], sl[j]), sc[j], sf[j]);
-    }
-    return r;
-}
-
-// Welford/Chan merge of two partial (count, mean, M2) statistics; (0,*,*) is the neutral element
+// Welford/Chan merge of two partial (count, mean, M2) statistics; (0,*,*) is the neutral element.  Not st_merge (conv_st.hip):
+// a branch and an IEEE division here, branch-free on rcp there; the bits differ, so neither replaces the other.
 __device__ __forceinline__ void cg_merge(float& n, float& mean, float& m2, float nb, float meanb, float m2b) {
     const float nt = n + nb;
     if (nt > 0.0f) {
@@ -87,36 +68,6 @@ __device__ __forceinline__ void cg_merge(float& n, float& mean, float& m2, float
         m2 = m2 + m2b + delta * delta * n * fb;
     }
     n = nt;
-}
-
-__device__ __forceinline__ float cg_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-// q / n for 0 <= q < 2^22 via the fp32 reciprocal, exact after one correction
-__device__ __forceinline__ int cg_div(int q, int n, float inv_n) {
-    int t = (int)((float)q * inv_n);
-    if (t * n > q) --t;
-    if ((t + 1) * n <= q) ++t;
-    return t;
-}
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// two fp32 -> packed bf16 (round to nearest even: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned cg_bf2(float x0, float x1) {
-    const bf16x2 v = {(__bf16)x0, (__bf16)x1};
-    return __builtin_bit_cast(unsigned, v);
-}
-
-// x = hi + lo with hi = x truncated to fp16 and lo = fp16(x - hi), two elements at a time
-// (v_cvt_pkrtz_f16_f32; fp16 subnormals are honoured by the f16 MFMA, probed on gfx950).
-__device__ __forceinline__ void cg_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
-    const h16x2 h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-    const h16x2 l = __builtin_amdgcn_cvt_pkrtz(x0 - (float)h[0], x1 - (float)h[1]);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
 }
 
 // WIDE (bf16 products, gather pipeline, one unit per stage, no fused transform): every source is STORED as bf16 and walked in
@@ -249,7 +200,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     for (int p = 0; p < MI; ++p) {
         const int q = q0 + srow + 64 * p;
         a_ok[p] = q < Q;
-        const int t = a_ok[p] ? cg_div(q, d.No, inv_no) : 0;
+        const int t = a_ok[p] ? eab_div(q, d.No, inv_no) : 0;
         const int o = a_ok[p] ? q - t * d.No : 0;
         a_t[p] = t;
         a_f0[p] = o * d.istride;
@@ -299,8 +250,8 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         const int hi_need = (d.No - 1) * d.istride + io_max - (d.Fin - 1);
         const int Fp = d.Fin + halo_lo + (hi_need > 0 ? hi_need : 0);
         const float inv_fp = 1.0f / (float)Fp;
-        const int t_first = cg_div(q0, d.No, inv_no);
-        const int t_last = cg_div((q0 + BM < Q ? q0 + BM : (Q > q0 ? Q : q0 + 1)) - 1, d.No, inv_no);
+        const int t_first = eab_div(q0, d.No, inv_no);
+        const int t_last = eab_div((q0 + BM < Q ? q0 + BM : (Q > q0 ? Q : q0 + 1)) - 1, d.No, inv_no);
         const int P = (t_last - t_first + 1 - dt_min) * Fp;          // <= CG_PMAX (checked on the host)
 
         int p_tf[PP];
@@ -308,7 +259,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
         for (int pp = 0; pp < PP; ++pp) {
             const int pidx = srow + 64 * pp;
-            const int tr = cg_div(pidx, Fp, inv_fp);
+            const int tr = eab_div(pidx, Fp, inv_fp);
             const int t_in = t_first + dt_min + tr, fi = pidx - tr * Fp - halo_lo;
             p_ok[pp] = pidx < P && t_in >= 0 && t_in < d.T && fi >= 0 && fi < d.Fin;
             p_tf[pp] = t_in * d.Fin + fi;
@@ -318,7 +269,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         for (int mi = 0; mi < MI; ++mi) {
             int q = q0 + (wm * MI + mi) * 32 + li;
             q = q < Q ? q : (Q > q0 ? Q - 1 : q0);                   // tile tail: any row of the tile's patch (masked in the epilogue)
-            const int t = cg_div(q, d.No, inv_no), o = q - t * d.No;
+            const int t = eab_div(q, d.No, inv_no), o = q - t * d.No;
             fa[mi] = ((t - t_first - dt_min) * Fp + o * d.istride + halo_lo) * LDK + 4 * lh;
         }
         const int b_base = (wn * NI * 32 + li) * LDK + 4 * lh;
@@ -335,7 +286,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             p_tc = ((second ? 1 : 0) << 8) | (cok ? c : 0);
 #pragma unroll
             for (int pp = 0; pp < PP; ++pp) {
-                const unsigned off = (p_ok[pp] && cok) ? (unsigned)((p_tf[pp] * Cs + c) * 4) : CG_OOB;
+                const unsigned off = (p_ok[pp] && cok) ? (unsigned)((p_tf[pp] * Cs + c) * 4) : EAB_OOB;
                 const u32x4 v = second ? __builtin_amdgcn_raw_buffer_load_b128(rs1, off, 0, 0)
                                        : __builtin_amdgcn_raw_buffer_load_b128(rs0, off, 0, 0);
                 rp[pp] = __builtin_bit_cast(f32x4, v);
@@ -355,16 +306,16 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                 if (pidx >= CG_PMAX) continue;
                 f32x4 v = rp[pp];
                 if (XF != EAB_XF_NONE) {
-                    const f32x4 x = cg_xform<XF>(v, sh01, sh23, sl);
+                    const f32x4 x = eab_xform<XF>(v, sh01, sh23, sl);
                     v = p_ok[pp] ? x : f32x4{0.f, 0.f, 0.f, 0.f};     // halo / causal zeros stay exactly 0
                 }
                 float* arow = &sm.a[pidx * LDK];
                 if (BF) {
-                    *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + skq * 8) = make_uint2(cg_bf2(v[0], v[1]), cg_bf2(v[2], v[3]));
+                    *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + skq * 8) = make_uint2(eab_bf2(v[0], v[1]), eab_bf2(v[2], v[3]));
                 } else if (H3) {
                     unsigned h01, l01, h23, l23;
-                    cg_split2(v[0], v[1], h01, l01);
-                    cg_split2(v[2], v[3], h23, l23);
+                    eab_split2(v[0], v[1], h01, l01);
+                    eab_split2(v[2], v[3], h23, l23);
                     *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + skq * 8) = make_uint2(h01, h23);
                     *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + 32 + skq * 8) = make_uint2(l01, l23);
                 } else {
@@ -383,7 +334,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                 float* brow = &sm.b[buf][(srow + 64 * p) * LDK];
                 if (BF) {
                     *reinterpret_cast<uint2*>(reinterpret_cast<char*>(brow) + skq * 8) =
-                        make_uint2(cg_bf2(rbw[p][0], rbw[p][1]), cg_bf2(rbw[p][2], rbw[p][3]));
+                        make_uint2(eab_bf2(rbw[p][0], rbw[p][1]), eab_bf2(rbw[p][2], rbw[p][3]));
                 } else if (H3) {
                     const u32x4 w = __builtin_bit_cast(u32x4, rbw[p]);
                     *reinterpret_cast<uint2*>(reinterpret_cast<char*>(brow) + skq * 8) = make_uint2(w[0], w[1]);
@@ -552,7 +503,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             for (int p = 0; p < MI; ++p) {
                 const bool ok = tap_ok[p] && cok;
                 rg.st_ok[0][p] = ok;
-                const unsigned off = ok ? (second ? tap_b1[p] : tap_b0[p]) : CG_OOB;
+                const unsigned off = ok ? (second ? tap_b1[p] : tap_b0[p]) : EAB_OOB;
                 // (bf16 source: eight bf16 of the row = the LDS image of this thread's part of the unit; soffset in bytes)
                 const u32x4 v = second ? __builtin_amdgcn_raw_buffer_load_b128(rs1, off, cu * (half ? 2 : 4), 0)
                                        : __builtin_amdgcn_raw_buffer_load_b128(rs0, off, cu * (half ? 2 : 4), 0);
@@ -607,7 +558,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             for (int p = 0; p < MI; ++p) {
                 const bool ok = tap_ok[p] && cok;
                 rg.st_ok[ku][p] = ok;
-                const unsigned off = ok ? (second ? tap_b1[p] : tap_b0[p]) + (unsigned)(c * 4) : CG_OOB;
+                const unsigned off = ok ? (second ? tap_b1[p] : tap_b0[p]) + (unsigned)(c * 4) : EAB_OOB;
                 if (VEC) {
                     const u32x4 v = second ? __builtin_amdgcn_raw_buffer_load_b128(rs1, off, 0, 0)
                                            : __builtin_amdgcn_raw_buffer_load_b128(rs0, off, 0, 0);
@@ -616,7 +567,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                     // channel counts that are not multiples of 4 (odd microphone counts): dword gathers
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const unsigned oj = (ok && c + j < Cs) ? off + 4u * j : CG_OOB;
+                        const unsigned oj = (ok && c + j < Cs) ? off + 4u * j : EAB_OOB;
                         const unsigned v = second ? __builtin_amdgcn_raw_buffer_load_b32(rs1, oj, 0, 0)
                                                   : __builtin_amdgcn_raw_buffer_load_b32(rs0, oj, 0, 0);
                         rg.ra[ku][p][j] = __builtin_bit_cast(float, v);
@@ -670,7 +621,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                 for (int k = 0; k < (DUAL ? 2 : 1); ++k) {
                     f32x4 v = rg.ra[ku][p];
                     if (XF != EAB_XF_NONE) {
-                        v = cg_xform<XF>(v, sh01[k], sh23[k], sl[k]);
+                        v = eab_xform<XF>(v, sh01[k], sh23[k], sl[k]);
                         if (!all_ok) {                           // scalar branch (the asm keeps it one: four selects otherwise)
                             asm volatile("; rim" ::: "memory");
                             v = rg.st_ok[ku][p] ? v : f32x4{0.f, 0.f, 0.f, 0.f};
@@ -682,12 +633,12 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                         if (half)                                                // eight channels of a 32-channel unit
                             *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(arow) + skq * 16) = __builtin_bit_cast(u32x4, v);
                         else
-                            *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + skq * 8) = make_uint2(cg_bf2(v[0], v[1]), cg_bf2(v[2], v[3]));
+                            *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + skq * 8) = make_uint2(eab_bf2(v[0], v[1]), eab_bf2(v[2], v[3]));
                     } else if (H3) {
                         // unit layout in LDS (64 B): 16 fp16 hi | 16 fp16 lo; this thread owns channels 4*skq..+3
                         unsigned h01, l01, h23, l23;
-                        cg_split2(v[0], v[1], h01, l01);
-                        cg_split2(v[2], v[3], h23, l23);
+                        eab_split2(v[0], v[1], h01, l01);
+                        eab_split2(v[2], v[3], h23, l23);
                         *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + skq * 8) = make_uint2(h01, h23);
                         *reinterpret_cast<uint2*>(reinterpret_cast<char*>(arow) + 32 + skq * 8) = make_uint2(l01, l23);
                     } else {
@@ -702,10 +653,10 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                     if constexpr (WIDE) {                        // wide stage: eight weights of the thread -> 16 bytes
                         const f32x4 r0 = rg.rb[ku][p], r1 = rg.rb2[BF ? p : 0];
                         *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(brow) + skq * 16) =
-                            u32x4{cg_bf2(r0[0], r0[1]), cg_bf2(r0[2], r0[3]), cg_bf2(r1[0], r1[1]), cg_bf2(r1[2], r1[3])};
+                            u32x4{eab_bf2(r0[0], r0[1]), eab_bf2(r0[2], r0[3]), eab_bf2(r1[0], r1[1]), eab_bf2(r1[2], r1[3])};
                     } else {
                         *reinterpret_cast<uint2*>(reinterpret_cast<char*>(brow) + skq * 8) =
-                            make_uint2(cg_bf2(rg.rb[ku][p][0], rg.rb[ku][p][1]), cg_bf2(rg.rb[ku][p][2], rg.rb[ku][p][3]));
+                            make_uint2(eab_bf2(rg.rb[ku][p][0], rg.rb[ku][p][1]), eab_bf2(rg.rb[ku][p][2], rg.rb[ku][p][3]));
                     }
                 } else if (H3) {   // global: [4 hi | 4 lo] per 4-channel group  ->  LDS: [16 hi | 16 lo] per unit
                     const u32x4 w = __builtin_bit_cast(u32x4, rg.rb[ku][p]);
@@ -910,7 +861,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const int qg = q0 + (wm * MI + mi) * 32 + 8 * r4 + 4 * lh;     // rows 4*r4 + j, j = 0..3: consecutive q
-                    const int t = cg_div((FULL || qg < Q) ? qg : 0, d.No, inv_no);
+                    const int t = eab_div((FULL || qg < Q) ? qg : 0, d.No, inv_no);
                     int o = ((FULL || qg < Q) ? qg : 0) - t * d.No;
                     unsigned row_start = (unsigned)t * row_bytes;
                     unsigned cur = row_start + (unsigned)o * step_bytes;            // byte offset of out[t][2o][0]
@@ -921,8 +872,8 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                         const bool ok1 = ok0 && 2 * o + 1 < d.Fout;
                         const float v0 = acc[mi][0][r] + bias_v[0], v1 = acc[mi][1][r] + bias_v[1];
                         const unsigned o0 = cur + 4u * ch[0];
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), r_dst, ok0 ? o0 : CG_OOB, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), r_dst, ok1 ? o0 + chan_bytes : CG_OOB, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), r_dst, ok0 ? o0 : EAB_OOB, 0, 0);
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), r_dst, ok1 ? o0 + chan_bytes : EAB_OOB, 0, 0);
                         const float e0 = eab_prelu(v0, a) - k0, e1 = eab_prelu(v1, a) - k0;
                         const float m0 = FULL ? e0 : (ok0 ? e0 : 0.0f), m1 = ok1 ? e1 : 0.0f;
                         su += m0;
@@ -964,7 +915,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const int qg = q0 + (wm * MI + mi) * 32 + 8 * r4 + 4 * lh;
-                    const int t = cg_div(qg, d.No, inv_no);
+                    const int t = eab_div(qg, d.No, inv_no);
                     int o = qg - t * d.No;
                     unsigned row_start = (unsigned)t * row_bytes + phase_bytes;
                     unsigned cur = row_start + (unsigned)o * step_bytes;
@@ -993,7 +944,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                     for (int c = 0; c < NC; ++c) {
                         float v;
                         if constexpr (GLU) {
-                            const float av = acc[mi][0][r] + bias_v[0], sv = cg_sigmoid(acc[mi][1][r] + bias_v[1]);
+                            const float av = acc[mi][0][r] + bias_v[0], sv = eab_fast_sigmoid(acc[mi][1][r] + bias_v[1]);
                             v = av * sv;
                             if (DUMPV) {
                                 float* dp = d.glu_dump + 2 * (out_b + (off[r] >> 2)) + n_blk + wn * 64 + li;
@@ -1043,7 +994,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         for (int r4 = 0; r4 < 4; ++r4) {
             // rows r = 4*r4 + j, j = 0..3 are consecutive q: one division per group of four
             const int qg = q0 + (wm * MI + mi) * 32 + 8 * r4 + 4 * lh;
-            const int t = cg_div(qg < Q ? qg : 0, d.No, inv_no);
+            const int t = eab_div(qg < Q ? qg : 0, d.No, inv_no);
             int o = (qg < Q ? qg : 0) - t * d.No;
             // byte offset of (t, o) stepped incrementally: two integer multiplies per group of four rows
             // instead of three per row (v_mul_lo_u32 is quarter rate and shares the pipe with the fp32 MFMA)
@@ -1053,7 +1004,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             for (int j = 0; j < 4; ++j) {
                 const int r = 4 * r4 + j;
                 rowok[r] = qg + j < Q;
-                off[r] = rowok[r] ? cur : CG_OOB;
+                off[r] = rowok[r] ? cur : EAB_OOB;
                 cur += step_bytes;
                 if (++o == d.No) {
                     o = 0;
@@ -1069,7 +1020,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     auxv[r][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                               r_aux, rowok[r] ? off[r] + 4u * ch[c] : CG_OOB, 0, 0));
+                                                               r_aux, rowok[r] ? off[r] + 4u * ch[c] : EAB_OOB, 0, 0));
         }
         if (d.dst_acc) {
 #pragma unroll
@@ -1077,7 +1028,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     accv[r][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                               r_acc, rowok[r] ? off[r] + 4u * ch[c] : CG_OOB, 0, 0));
+                                                               r_acc, rowok[r] ? off[r] + 4u * ch[c] : EAB_OOB, 0, 0));
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1085,7 +1036,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             for (int c = 0; c < NC; ++c) {
                 float v;
                 if (GLU) {
-                    const float av = acc[mi][0][r] + bias_v[0], sv = cg_sigmoid(acc[mi][1][r] + bias_v[1]);
+                    const float av = acc[mi][0][r] + bias_v[0], sv = eab_fast_sigmoid(acc[mi][1][r] + bias_v[1]);
                     v = av * sv;
                     if (d.glu_dump && rowok[r]) {
                         // training: value and sigmoid(gate) in the packed column order (what eab_glu_bwd_f32 reads)
@@ -1097,9 +1048,9 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                     v = acc[mi][c][r] + bias_v[c];
                 }
                 if (d.epi == EAB_EPI_RELU) v = fmaxf(v, 0.0f);
-                else if (d.epi == EAB_EPI_MULSIG) v = auxv[r][c] * cg_sigmoid(v);
+                else if (d.epi == EAB_EPI_MULSIG) v = auxv[r][c] * eab_fast_sigmoid(v);
                 else if (d.epi == EAB_EPI_ADD) v = v + auxv[r][c];
-                const unsigned o4 = rowok[r] ? off[r] + 4u * ch[c] : CG_OOB;
+                const unsigned o4 = rowok[r] ? off[r] + 4u * ch[c] : EAB_OOB;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r_dst, o4, 0, 0);
                 if (d.dst_acc)
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v + accv[r][c]), r_acc, o4, 0, 0);

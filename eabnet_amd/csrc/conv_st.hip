@@ -24,31 +24,17 @@
 //
 // Every output row is one fmaf chain in a fixed k order, independent of the tile it falls into: streamed frames stay
 // bit-identical to the offline pass (eab_time_window), as with conv_gemm_kernel.
-#include "common.h"
+#include "device.h"
 #include <atomic>
 #include <type_traits>
 
 #define ST_THREADS 256
-#define ST_OOB 0x80000000u
 #define ST_XFC 128          // max channels of a source that carries a fused transform
 #define ST_PLAIN 0
 #define ST_DUAL 1           // EAB_EPI_DUALGATE: value / gate columns see the same source through two transforms
 #define ST_GLU 2            // EAB_EPI_GLU: value / gate columns of ONE convolution (GateConv2d / GateConvTranspose2d)
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float st_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-
-// q / n for 0 <= q < 2^22 via the fp32 reciprocal, exact after one correction (as in conv_gemm.hip)
-__device__ __forceinline__ int st_div(int q, int n, float inv_n) {
-    int t = (int)((float)q * inv_n);
-    if (t * n > q) --t;
-    if ((t + 1) * n <= q) ++t;
-    return t;
-}
-
-// Welford/Chan merge, (0,*,*) neutral
+// Welford/Chan merge, (0,*,*) neutral.  Not cg_merge (conv_gemm.hip), which branches and divides:
 __device__ __forceinline__ void st_merge(float& n, float& mean, float& m2, float nb, float meanb, float m2b) {
     // branch-free; counts are small integers, so rcp (1 ulp) instead of an IEEE division chain is exact enough for a
     // quantity that only feeds a normalisation -- and the same bits in every workgroup, which is what matters
@@ -60,35 +46,12 @@ __device__ __forceinline__ void st_merge(float& n, float& mean, float& m2, float
     n = nt;
 }
 
-typedef __bf16 st_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 st_bf16x2 __attribute__((ext_vector_type(2)));
-// two fp32 -> packed bf16 (round to nearest even: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned st_bf2(float x0, float x1) {
-    const st_bf16x2 v = {(__bf16)x0, (__bf16)x1};
-    return __builtin_bit_cast(unsigned, v);
-}
-
 // buffer descriptor from wave-uniform inputs, made provably uniform for the compiler (MI355X guide, T20)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t st_rsrc(const float* p, unsigned bytes) {
     const unsigned long long a = reinterpret_cast<unsigned long long>(p);
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
     const unsigned nb = __builtin_amdgcn_readfirstlane(bytes);
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(((unsigned long long)hi << 32) | lo), 0, nb, 0x00020000);
-}
-
-template <int XF>
-__device__ __forceinline__ f32x4 st_xform(f32x4 v, f32x4 sh01, f32x4 sh23, f32x4 sl) {
-    const float sc[4] = {sh01[0], sh01[2], sh23[0], sh23[2]};
-    const float sf[4] = {sh01[1], sh01[3], sh23[1], sh23[3]};
-    f32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (XF == EAB_XF_NORM_PRELU)
-            r[j] = eab_prelu(fmaf(v[j], sc[j], sf[j]), sl[j]);
-        else
-            r[j] = fmaf(eab_prelu(v[j], sl[j]), sc[j], sf[j]);
-    }
-    return r;
 }
 
 // dynamic LDS: [NA][BM][LD] floats of A, then the tables

@@ -136,7 +136,7 @@
             const int q = q0 + (tid >> SH4) + j * RPS;
             rw.ok[j] = q < Q;
             const int qc = rw.ok[j] ? q : Qm1;
-            const int t = st_div(qc, No, inv_no);
+            const int t = eab_div(qc, No, inv_no);
             rw.t[j] = t;
             rw.f[j] = (qc - t * No) * d.istride;
         }
@@ -153,7 +153,7 @@
             for (int j = 0; j < NS; ++j) {
                 const int ti = rw.t[j] + tp.x, fi = rw.f[j] + tp.y;
                 const bool ok = live & rw.ok[j] & (ti >= 0) & (ti < d.T) & (fi >= 0) & (fi < d.Fin);
-                const unsigned off = ok ? (unsigned)(((ti * d.Fin + fi) * Cs + c) * 4) : ST_OOB;
+                const unsigned off = ok ? (unsigned)(((ti * d.Fin + fi) * Cs + c) * 4) : EAB_OOB;
                 bt.ok[tt * NS + j] = ok;
                 bt.v[tt * NS + j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
             }
@@ -183,7 +183,7 @@
                     for (int a = 0; a < NA; ++a) {
                         f32x4 x = bt.v[tt * NS + j];
                         if (XF != EAB_XF_NONE) {
-                            x = st_xform<XF>(x, sh01[a], sh23[a], sl[a]);
+                            x = eab_xform<XF>(x, sh01[a], sh23[a], sl[a]);
                             x = bt.ok[tt * NS + j] ? x : f32x4{0.f, 0.f, 0.f, 0.f};   // zero padding acts on the NORMALISED tensor
                         }
                         if constexpr (BF) {
@@ -194,8 +194,8 @@
                             const int blk = k0 & ~31, r32 = k0 & 31;
                             const int pos = blk + 8 * ((r32 & 7) >> 1) + 4 * (r32 >> 4) + 2 * ((r32 >> 3) & 1);
                             unsigned short* hrow = sh + (a * BM + (tid >> SH4) + j * RPS) * LD;
-                            *reinterpret_cast<unsigned*>(hrow + pos) = st_bf2(x[0], x[1]);
-                            *reinterpret_cast<unsigned*>(hrow + pos + 8) = st_bf2(x[2], x[3]);
+                            *reinterpret_cast<unsigned*>(hrow + pos) = eab_bf2(x[0], x[1]);
+                            *reinterpret_cast<unsigned*>(hrow + pos + 8) = eab_bf2(x[2], x[3]);
                         } else {
                             *reinterpret_cast<f32x4*>(dst + a * BM * LD) = x;
                         }
@@ -343,7 +343,7 @@
 #pragma unroll
         for (int ua = 0; ua < UB; ua += UAB) {
             if (ua < M32) {                              // workgroup-uniform
-                st_bf16x8 ah[UAB][NA][RB];
+                bf16x8 ah[UAB][NA][RB];
 #pragma unroll
                 for (int sI = 0; sI < UAB; ++sI) {
                     const int uc = ua + sI < M32 ? ua + sI : M32 - 1;
@@ -351,7 +351,7 @@
                     for (int a = 0; a < NA; ++a)
 #pragma unroll
                         for (int rb = 0; rb < RB; ++rb)
-                            ah[sI][a][rb] = *reinterpret_cast<const st_bf16x8*>(h_lane + (a * BM + rb * 16) * LD + 32 * uc);
+                            ah[sI][a][rb] = *reinterpret_cast<const bf16x8*>(h_lane + (a * BM + rb * 16) * LD + 32 * uc);
                 }
 #pragma unroll
                 for (int sI = 0; sI < UAB; ++sI) {
@@ -360,8 +360,8 @@
 #pragma unroll
                         for (int cb = 0; cb < NCB; ++cb) {
                             const f32x4 w0 = bq[2 * u < U ? 2 * u : 0][cb], w1 = bq[2 * u + 1 < U ? 2 * u + 1 : 0][cb];
-                            const u32x4 bw = {st_bf2(w0[0], w0[1]), st_bf2(w0[2], w0[3]), st_bf2(w1[0], w1[1]), st_bf2(w1[2], w1[3])};
-                            const st_bf16x8 bh = __builtin_bit_cast(st_bf16x8, bw);
+                            const u32x4 bw = {eab_bf2(w0[0], w0[1]), eab_bf2(w0[2], w0[3]), eab_bf2(w1[0], w1[1]), eab_bf2(w1[2], w1[3])};
+                            const bf16x8 bh = __builtin_bit_cast(bf16x8, bw);
 #pragma unroll
                             for (int rb = 0; rb < RB; ++rb)
                                 acc[u & 1][rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[sI][DUAL ? cb : 0][rb], bh,
@@ -457,14 +457,14 @@
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
         const int qg = q0 + rb * 16 + 4 * kq;            // four consecutive rows
-        const int t = st_div(qg < Q ? qg : 0, No, inv_no);
+        const int t = eab_div(qg < Q ? qg : 0, No, inv_no);
         int o = (qg < Q ? qg : 0) - t * No;
         unsigned row_start = (unsigned)t * row_bytes + phase_bytes;
         unsigned cur = row_start + (unsigned)o * step_bytes;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             rowok[rb][r] = qg + r < Q;
-            off[rb][r] = rowok[rb][r] ? cur : ST_OOB;
+            off[rb][r] = rowok[rb][r] ? cur : EAB_OOB;
             cur += step_bytes;
             if (++o == No) {
                 o = 0;
@@ -482,7 +482,7 @@
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     auxv[rb][r][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                   r_aux, rowok[rb][r] ? off[rb][r] + 4u * ch[c] : ST_OOB, 0, 0));
+                                                                   r_aux, rowok[rb][r] ? off[rb][r] + 4u * ch[c] : EAB_OOB, 0, 0));
     }
     if (d.dst_acc) {
 #pragma unroll
@@ -492,7 +492,7 @@
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     accv[rb][r][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                                   r_acc, rowok[rb][r] ? off[rb][r] + 4u * ch[c] : ST_OOB, 0, 0));
+                                                                   r_acc, rowok[rb][r] ? off[rb][r] + 4u * ch[c] : EAB_OOB, 0, 0));
     }
     float st_slope[2][NC];
 #pragma unroll
@@ -523,13 +523,13 @@
             for (int c = 0; c < NC; ++c) {
                 float v;
                 if constexpr (GATED) {
-                    v = (acc[0][rb][0][r] + bias_v[0]) * st_sigmoid(acc[0][rb][1][r] + bias_v[1]);
+                    v = (acc[0][rb][0][r] + bias_v[0]) * eab_fast_sigmoid(acc[0][rb][1][r] + bias_v[1]);
                 } else {
                     v = acc[0][rb][c][r] + bias_v[c];
                 }
                 if (d.epi == EAB_EPI_RELU) v = fmaxf(v, 0.0f);
                 else if (d.epi == EAB_EPI_ADD) v = v + auxv[rb][r][c];
-                const unsigned o4 = rowok[rb][r] ? off[rb][r] + 4u * ch[c] : ST_OOB;
+                const unsigned o4 = rowok[rb][r] ? off[rb][r] + 4u * ch[c] : EAB_OOB;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r_dst, o4, 0, 0);
                 if (F2OK && f2) t2[(rb * 16 + 4 * kq + r) * LD2 + ch[c]] = v;      // A operand of the fused second convolution
                 if (d.dst_acc)
@@ -642,7 +642,7 @@
                     const bool okr = q < Q;
                     const float v2 = acc2[0][rb][r] + acc2[1][rb][r];
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v2), r_d2,
-                                                          okr ? (unsigned)((q * N2 + ch2) * 4) : ST_OOB, 0, 0);
+                                                          okr ? (unsigned)((q * N2 + ch2) * 4) : EAB_OOB, 0, 0);
                     if (d.f2_stats && okr) {
                         const bool first = cnt2 == 0.0f;
 #pragma unroll

@@ -1,8 +1,6 @@
 // K13: complex filter-and-sum  Y = sum_m W_m * X_m  (reference EaBNet.py:114-117),
 // and K12b+K13 fused: second Linear of w_dnn + filter-and-sum (EaBNet.py:596,613-117).
-#include "common.h"
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "device.h"
 
 // Four lanes per TF bin: lane p multiplies microphones p, p+4, ... and the quad is reduced with two xor-shuffles, so a wave
 // reads 16 bins x M x 8 B = one contiguous block of W and of X per load (one thread per bin -- the first version -- had every

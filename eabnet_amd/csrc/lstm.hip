@@ -23,34 +23,13 @@
 //   * x is fetched from HBM four steps ahead (one contiguous 4 KB block of the
 //     channels-last tensor per workgroup); h_t leaves as one coalesced 4 KB store.
 // Bound: fp32 matrix pipe.
-#include "common.h"
+#include "device.h"
 #include <cstdlib>
 #include <type_traits>
 
 #define LS_H 64
 #define LS_SEQ 16
 #define LS_LD (LS_H + 4)   // 272-byte rows: odd 16-byte-slot stride -> conflict-free b128 fragment reads
-
-// sigmoid / tanh on the hardware exp and rcp (1 ulp class): abs error ~2e-7,
-// three orders of magnitude inside the 1e-4 parity bar, and short enough to hide
-// under the input-half MFMAs.
-__device__ __forceinline__ float ls_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ls_tanh(float x) { return fmaf(2.0f, ls_sigmoid(2.0f * x), -1.0f); }
-
-// sum over the 16 lanes of a DPP row; every lane ends with the total
-__device__ __forceinline__ float ls_row_sum(float v) {
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
-    v += dpp(v, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
-    v += dpp(v, std::integral_constant<int, 0x141>{});   // row_half_mirror
-    v += dpp(v, std::integral_constant<int, 0x140>{});   // row_mirror
-    return v;
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define LS_OOB 0x80000000u   // byte offset outside every legal tensor (host checks < 2^31): loads give 0, stores drop
 
 template <bool LN, bool DUMP>
 __global__ __launch_bounds__(256) void lstm64_kernel(const float* __restrict__ x, const float* __restrict__ ln_g,
@@ -109,15 +88,15 @@ __global__ __launch_bounds__(256) void lstm64_kernel(const float* __restrict__ x
     }
 
     auto load_x = [&](int t) -> f32x4 {
-        const unsigned off = (sv && t < t_hi) ? seq_off + (unsigned)t * t_stride : LS_OOB;
+        const unsigned off = (sv && t < t_hi) ? seq_off + (unsigned)t * t_stride : EAB_OOB;
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
     };
     auto norm_store = [&](f32x4 v, int buf) {
         if (LN) {
             // LayerNorm over the 64 channels = 16 lanes x 4, two-pass in registers
-            const float mean = ls_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
+            const float mean = eab_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
             f32x4 dlt = {v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
-            const float q = ls_row_sum((dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]));
+            const float q = eab_row_sum((dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]));
             const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + ln_eps);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = dlt[j] * rstd * g4[j] + b4[j];
@@ -147,7 +126,7 @@ __global__ __launch_bounds__(256) void lstm64_kernel(const float* __restrict__ x
     // prologue: h_{t_lo-1}, c_{t_lo-1} (zero at the start of the utterance), x_{t_lo} and x_{t_lo+1}
     // normalised in LDS, accx = b + W_x x_{t_lo}
     *reinterpret_cast<f32x4*>(&hs[0][ls * LS_LD + lc]) = __builtin_bit_cast(
-        f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, (sv && t_lo > 0) ? seq_off + (unsigned)(t_lo - 1) * t_stride : LS_OOB, 0, 0));
+        f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, (sv && t_lo > 0) ? seq_off + (unsigned)(t_lo - 1) * t_stride : EAB_OOB, 0, 0));
     norm_store(load_x(t_lo), 0);
     norm_store(load_x(t_lo + 1), 1);
     const int u = wave * 16 + ln;
@@ -256,7 +235,7 @@ __global__ __launch_bounds__(256) void lstm64_kernel(const float* __restrict__ x
         // ---- X2: second half of the input MFMAs covers the barrier and the LDS latency
         mma(xf, wx, accx, I2{}, I4{});
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), rh,
-                                               sv ? seq_off + (unsigned)t * t_stride : LS_OOB, 0, 0);   // coalesced 4 KB
+                                               sv ? seq_off + (unsigned)t * t_stride : EAB_OOB, 0, 0);   // coalesced 4 KB
         xq = xr;
         xr = xn;
     }
@@ -336,14 +315,14 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
         b4 = *reinterpret_cast<const f32x4*>(ln_b + lc);
     }
     auto load_x = [&](int t) -> f32x4 {
-        const unsigned off = (sv && t < t_hi) ? seq_off + (unsigned)t * t_stride : LS_OOB;
+        const unsigned off = (sv && t < t_hi) ? seq_off + (unsigned)t * t_stride : EAB_OOB;
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
     };
     auto norm_store = [&](f32x4 v, int buf) {
         if (LN) {
-            const float mean = ls_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
+            const float mean = eab_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
             f32x4 dlt = {v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
-            const float q = ls_row_sum((dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]));
+            const float q = eab_row_sum((dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]));
             const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + ln_eps);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = dlt[j] * rstd * g4[j] + b4[j];
@@ -357,7 +336,7 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
     // prologue: h_{t_lo-1}, c_{t_lo-1}, x_{t_lo} normalised in LDS; x_{t_lo+1}, x_{t_lo+2} raw in registers
     if (ls < NSEQ)
         *reinterpret_cast<f32x4*>(&hs[0][ls * LS_LD + lc]) = __builtin_bit_cast(
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, (sv && t_lo > 0) ? seq_off + (unsigned)(t_lo - 1) * t_stride : LS_OOB, 0, 0));
+            f32x4, __builtin_amdgcn_raw_buffer_load_b128(rh, (sv && t_lo > 0) ? seq_off + (unsigned)(t_lo - 1) * t_stride : EAB_OOB, 0, 0));
     norm_store(load_x(t_lo), 0);
     float cst[G][4];
 #pragma unroll
@@ -423,7 +402,7 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
                 const float gi = quad(a, std::integral_constant<int, 0x00>{}), gf = quad(a, std::integral_constant<int, 0x55>{});
                 const float gg = quad(a, std::integral_constant<int, 0xAA>{}), go = quad(a, std::integral_constant<int, 0xFF>{});
                 cst[q][s] = fmaf(gf, cst[q][s], gi * gg);
-                const float hv = go * ls_tanh(cst[q][s]);
+                const float hv = go * eab_fast_tanh(cst[q][s]);
                 if (s == gate) hs[nxt][(4 * q + s) * LS_LD + u] = hv;
                 if (DUMP) {
                     // training: gates[seq][t][5][64] = i, f, g, o, c (the layout csrc/lstm_bwd.hip reads): every lane its own
@@ -441,7 +420,7 @@ __global__ __launch_bounds__(256) void lstm64_q_kernel(const float* __restrict__
         if (ls < NSEQ) {
             const f32x4 hv4 = *reinterpret_cast<const f32x4*>(&hs[nxt][ls * LS_LD + lc]);
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv4), rh,
-                                                   sv ? seq_off + (unsigned)t * t_stride : LS_OOB, 0, 0);
+                                                   sv ? seq_off + (unsigned)t * t_stride : EAB_OOB, 0, 0);
         }
         xq = xr;
         xr = xn;

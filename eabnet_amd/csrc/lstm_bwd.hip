@@ -12,12 +12,11 @@
 //     dh_rec  = dgates_t . W_hh  as 64 v_mfma_f32_16x16x4_f32 per wave (K = 256; W_hh^T stationary in 64 VGPRs)
 // The activated gates and cell states come from the training forward (eab_lstm64_train_fwd_f32, gates [S][T][5][64]).
 // Bound: fp32 matrix pipe (64 MFMAs x 32 cycles per step), half of the forward's.
-#include "common.h"
+#include "device.h"
 
 #define LB_H 64
 #define LB_SEQ 16
 #define LB_LD (4 * LB_H + 4)      // dgates tile row: 256 floats + pad (odd 16-byte-slot stride)
-#define LB_OOB 0x80000000u
 #define LB_PF 3                    // steps of operands in flight in the 16-sequence reverse-time kernel (28 registers per step)
 // ... and in the 4-sequence kernel (7 registers per step).  Measured at 966 sequences, us per layer: 1 step of lead 870, 2: 997,
 // 3: 644, 4: 633, 5: 552, 8: 533, 12: 1843 (84 loads exceed the 6-bit vmcnt).  The latency to cover is ~3.5 us, far above an HBM
@@ -26,9 +25,7 @@
 
 #define LBB_ROW (4 * LB_H * 2 + 16) // the same tile as bf16: 512 bytes + pad (odd 16-byte-slot stride)
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 lb_bf16x8 __attribute__((ext_vector_type(8)));
-
+// not eab_fast_tanh (device.h): exp(-2x) in ONE multiply here, 2x negated inside the sigmoid there -- other instructions, the same value
 __device__ __forceinline__ float lb_tanh(float x) { return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f); }
 
 // BF (the bf16 training programs): dgates_t and W_hh rounded to bf16, dh_rec on 8 v_mfma_f32_16x16x32_bf16 per wave instead of
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
     // stationary operand: whT[4j+s] = W_hh[k = 16j + 4lk + s][u] = wcat[k][64 + u]
     // (BF: B fragments of the 16x16x32 form: whb[kb][j] = W_hh[k = 32kb + 8lk + j][u])
     float whT[BF ? 1 : 64];
-    lb_bf16x8 whb[BF ? 8 : 1];
+    bf16x8 whb[BF ? 8 : 1];
     if constexpr (BF) {
 #pragma unroll
         for (int kb = 0; kb < 8; ++kb)
@@ -151,7 +148,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
             const char* ab = &dgb[buf][ln * LBB_ROW + lk * 16];
 #pragma unroll
             for (int kb = 0; kb < 8; ++kb)
-                acc[kb & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const lb_bf16x8*>(ab + kb * 64), whb[kb], acc[kb & 3],
+                acc[kb & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*reinterpret_cast<const bf16x8*>(ab + kb * 64), whb[kb], acc[kb & 3],
                                                                      0, 0, 0);
         } else {
             const float* arow = &dg[buf][ln * LB_LD + 4 * lk];
@@ -219,17 +216,17 @@ __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restri
     const unsigned gb = (unsigned)(goff * 4), hb = (unsigned)(hoff * 4), g_tb = (unsigned)(g_t * 4), h_tb = (unsigned)(h_t * 4);
     auto load = [&](int t, float (&q)[7]) {
         const bool v = ok && t >= 0;
-        const unsigned go_ = v ? gb + (unsigned)t * g_tb : LB_OOB;
+        const unsigned go_ = v ? gb + (unsigned)t * g_tb : EAB_OOB;
         auto ld = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off) {
             return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
         };
         q[0] = ld(rs_g, go_);
-        q[1] = ld(rs_g, v ? go_ + LB_H * 4 : LB_OOB);
-        q[2] = ld(rs_g, v ? go_ + 2 * LB_H * 4 : LB_OOB);
-        q[3] = ld(rs_g, v ? go_ + 3 * LB_H * 4 : LB_OOB);
-        q[4] = ld(rs_g, v ? go_ + 4 * LB_H * 4 : LB_OOB);
-        q[5] = ld(rs_g, (v && t > 0) ? go_ - LB_H * 4 : LB_OOB);   // c_{t-1}: slot 4 of step t-1 sits 64 floats below slot 0 of step t
-        q[6] = ld(rs_h, v ? hb + (unsigned)t * h_tb : LB_OOB);
+        q[1] = ld(rs_g, v ? go_ + LB_H * 4 : EAB_OOB);
+        q[2] = ld(rs_g, v ? go_ + 2 * LB_H * 4 : EAB_OOB);
+        q[3] = ld(rs_g, v ? go_ + 3 * LB_H * 4 : EAB_OOB);
+        q[4] = ld(rs_g, v ? go_ + 4 * LB_H * 4 : EAB_OOB);
+        q[5] = ld(rs_g, (v && t > 0) ? go_ - LB_H * 4 : EAB_OOB);   // c_{t-1}: slot 4 of step t-1 sits 64 floats below slot 0 of step t
+        q[6] = ld(rs_h, v ? hb + (unsigned)t * h_tb : EAB_OOB);
     };
 #pragma unroll
     for (int k = 0; k < LBQ_PF; ++k) load(T - 1 - k, pf[k]);

@@ -14,32 +14,11 @@
 //     H-MFMAs (24) -> cell update (exp/rcp) -> h_t hi/lo -> LDS -> barrier -> fragments
 // and the input half (24 MFMAs of step t+1) is issued behind the barrier where it covers the
 // LDS round trip.
-#include "common.h"
+#include "device.h"
 #include <type_traits>
 
 #define LH_SEQ 16
 #define LH_ROW 272          // bytes: 2 k-blocks x (32 hi + 32 lo halves) + 16 pad (odd 16-byte-slot stride)
-#define LH_OOB 0x80000000u
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 h16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float lh_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float lh_tanh(float x) { return fmaf(2.0f, lh_sigmoid(2.0f * x), -1.0f); }
-
-__device__ __forceinline__ float lh_row_sum(float v) {     // sum over the 16 lanes of a DPP row
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    v += dpp(v, std::integral_constant<int, 0xB1>{});
-    v += dpp(v, std::integral_constant<int, 0x4E>{});
-    v += dpp(v, std::integral_constant<int, 0x141>{});
-    v += dpp(v, std::integral_constant<int, 0x140>{});
-    return v;
-}
 
 template <bool BF>
 __device__ __forceinline__ void lh_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
@@ -49,10 +28,7 @@ __device__ __forceinline__ void lh_split2(float x0, float x1, unsigned& hi, unsi
         hi = __builtin_bit_cast(unsigned, h);
         lo = __builtin_bit_cast(unsigned, l);
     } else {
-        const h16x2 h = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-        const h16x2 l = __builtin_amdgcn_cvt_pkrtz(x0 - (float)h[0], x1 - (float)h[1]);
-        hi = __builtin_bit_cast(unsigned, h);
-        lo = __builtin_bit_cast(unsigned, l);
+        eab_split2(x0, x1, hi, lo);
     }
 }
 
@@ -136,14 +112,14 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
     const int lrow = ls * LH_ROW + (lc >> 5) * 128 + (lc & 31) * 2;
 
     auto load_x = [&](int t) -> f32x4 {
-        const unsigned off = (sv && t < t_hi) ? seq_off + (unsigned)t * t_stride : LH_OOB;
+        const unsigned off = (sv && t < t_hi) ? seq_off + (unsigned)t * t_stride : EAB_OOB;
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
     };
     auto norm_store = [&](f32x4 v, int buf) {
         if (LN) {
-            const float mean = lh_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
+            const float mean = eab_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
             f32x4 dlt = {v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
-            const float q = lh_row_sum((dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]));
+            const float q = eab_row_sum((dlt[0] * dlt[0] + dlt[1] * dlt[1]) + (dlt[2] * dlt[2] + dlt[3] * dlt[3]));
             const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + ln_eps);
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[j] = dlt[j] * rstd * g4[j] + b4[j];
@@ -184,7 +160,7 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
     __syncthreads();
     if (t_lo > 0) {
         const f32x4 hp = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                       rh, sv ? seq_off + (unsigned)(t_lo - 1) * t_stride : LH_OOB, 0, 0));
+                                                       rh, sv ? seq_off + (unsigned)(t_lo - 1) * t_stride : EAB_OOB, 0, 0));
         unsigned h01, l01, h23, l23;
         lh_split2<BF>(hp[0], hp[1], h01, l01);
         lh_split2<BF>(hp[2], hp[3], h23, l23);
@@ -223,7 +199,7 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
     for (int r = 0; r < NR; ++r) {
         const int sq = s0 + row_seq(4 * lk + r);
         const int b = sq < S ? sq / F : 0, f = sq < S ? sq - b * F : 0;
-        hdir[r] = sq < S ? (unsigned)((((size_t)b * T * F + f) * 64 + u) * 4) : LH_OOB;
+        hdir[r] = sq < S ? (unsigned)((((size_t)b * T * F + f) * 64 + u) * 4) : EAB_OOB;
     }
     // training (DUMP): gates[seq][t][5][64] = activated i, f, g, o and the cell state (the layout csrc/lstm_bwd.hip reads)
     float* gdump[4];
@@ -252,12 +228,12 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
         char* hrow = &hs[nxt][hcol];
 #pragma unroll
         for (int r = 0; r < NR; ++r) {                  // lane holds unit u for the sequences of tile rows 4*lk + r
-            const float ig = lh_sigmoid(acc[0][r]);
-            const float fg = lh_sigmoid(acc[1][r]);
-            const float gg = lh_tanh(acc[2][r]);
-            const float og = lh_sigmoid(acc[3][r]);
+            const float ig = eab_fast_sigmoid(acc[0][r]);
+            const float fg = eab_fast_sigmoid(acc[1][r]);
+            const float gg = eab_fast_tanh(acc[2][r]);
+            const float og = eab_fast_sigmoid(acc[3][r]);
             cst[r] = fmaf(fg, cst[r], ig * gg);
-            const float h = og * lh_tanh(cst[r]);
+            const float h = og * eab_fast_tanh(cst[r]);
             if (DUMP && gdump[r]) {
                 float* gp = gdump[r] + (size_t)t * 320;
                 gp[0] = ig;
@@ -270,7 +246,7 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
             *reinterpret_cast<e16*>(hrow + (4 * lk + r) * LH_ROW) = hi;
             if (BF) {
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, h), rh,
-                                                      hdir[r] != LH_OOB ? hdir[r] + (unsigned)t * t_stride : LH_OOB, 0, 0);
+                                                      hdir[r] != EAB_OOB ? hdir[r] + (unsigned)t * t_stride : EAB_OOB, 0, 0);
             } else {
                 const e16 lo = (e16)(h - (float)hi);
                 *reinterpret_cast<e16*>(hrow + (4 * lk + r) * LH_ROW + 64) = lo;
@@ -291,7 +267,7 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
             const f32x4 hv = {lh_join<BF>(ph.x & 0xFFFF, pl.x & 0xFFFF), lh_join<BF>(ph.x >> 16, pl.x >> 16),
                               lh_join<BF>(ph.y & 0xFFFF, pl.y & 0xFFFF), lh_join<BF>(ph.y >> 16, pl.y >> 16)};
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hv), rh,
-                                                   sv ? seq_off + (unsigned)t * t_stride : LH_OOB, 0, 0);
+                                                   sv ? seq_off + (unsigned)t * t_stride : EAB_OOB, 0, 0);
         }
         xq = xr;
         xr = xn;

@@ -20,24 +20,10 @@
 // not depend on the load path.  Lanes are added by a fixed shuffle tree, the four waves in wave order through LDS, the spans in
 // index order by the final kernel.  No atomics.  Samples at or past a signal's length are never read.
 // Bound: launch latency and HBM (3 * L * 4 bytes per utterance; 4 * frames * F * 4 bytes for the loss).
-#include "common.h"
+#include "rows.h"
 
 #define SCORE_THREADS 256
 #define SCORE_SPAN 4096                       /* samples per workgroup: 4 rounds of 256 lanes x 4 samples */
-#define SCORE_MAX_LEN (1 << 30)
-
-// four consecutive values of a row at index i (a multiple of four); zero at and past len
-__device__ __forceinline__ void score_load4(const float* __restrict__ row, bool aligned, int i, int len, float v[4]) {
-    if (aligned && i + 4 <= len) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(row + i);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = i + k < len ? row[i + k] : 0.0f;
-    }
-}
-
-__device__ __forceinline__ bool score_aligned(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // acc[0..NQ) of all 256 lanes -> dst[0..NQ): shuffle tree in the wave, waves 0..3 in order
 template <int NQ>
@@ -57,34 +43,28 @@ __device__ __forceinline__ void score_reduce(double acc[NQ], double* __restrict_
     }
 }
 
-struct ScoreRows {
-    const float* p[3];            // estimate, clean, noisy
-    long long stride[3];          // floats between the rows of two utterances
-    int cap[3];                   // floats of a row that may be read
-};
-
-__device__ __forceinline__ int score_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+typedef EabRows<3> ScoreRows;       // estimate, clean, noisy
 
 __global__ __launch_bounds__(SCORE_THREADS) void energy_partial_kernel(const ScoreRows rows, const int32_t* __restrict__ lens,
                                                                        int spans, double* __restrict__ partial) {
     const int b = blockIdx.y, span = blockIdx.x;
-    const int le = score_clamp(lens[3 * b], rows.cap[0]), ls = score_clamp(lens[3 * b + 1], rows.cap[1]),
-              ly = score_clamp(lens[3 * b + 2], rows.cap[2]);
+    const int le = eab_clamp(lens[3 * b], rows.cap[0]), ls = eab_clamp(lens[3 * b + 1], rows.cap[1]),
+              ly = eab_clamp(lens[3 * b + 2], rows.cap[2]);
     const int longest = max(le, max(ls, ly));
     if ((long long)span * SCORE_SPAN >= longest) return;          // (workgroup-uniform) the final kernel does not read this row
     const float* e = rows.p[0] + (long long)b * rows.stride[0];
     const float* s = rows.p[1] + (long long)b * rows.stride[1];
     const float* y = rows.p[2] + (long long)b * rows.stride[2];
-    const bool ae = score_aligned(e), as = score_aligned(s), ay = score_aligned(y);
+    const bool ae = eab_aligned16(e), as = eab_aligned16(s), ay = eab_aligned16(y);
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < SCORE_SPAN / (4 * SCORE_THREADS); ++j) {
         const int i = span * SCORE_SPAN + j * 4 * SCORE_THREADS + 4 * (int)threadIdx.x;
         if (i < longest) {
             float ve[4], vs[4], vy[4];
-            score_load4(e, ae, i, le, ve);
-            score_load4(s, as, i, ls, vs);
-            score_load4(y, ay, i, ly, vy);
+            eab_load4(e, ae, i, le, ve);
+            eab_load4(s, as, i, ls, vs);
+            eab_load4(y, ay, i, ly, vy);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const double de = (double)ve[k], ds = (double)vs[k], dn = (double)vy[k] - (double)vs[k];
@@ -104,8 +84,8 @@ __global__ void energy_final_kernel(const double* __restrict__ partial, const in
                                     int B, int spans, double* __restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int le = score_clamp(lens[3 * b], rows.cap[0]), ls = score_clamp(lens[3 * b + 1], rows.cap[1]),
-              ly = score_clamp(lens[3 * b + 2], rows.cap[2]);
+    const int le = eab_clamp(lens[3 * b], rows.cap[0]), ls = eab_clamp(lens[3 * b + 1], rows.cap[1]),
+              ly = eab_clamp(lens[3 * b + 2], rows.cap[2]);
     const int longest = max(le, max(ls, ly));
     const int used = (int)(((long long)longest + SCORE_SPAN - 1) / SCORE_SPAN);
     double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -132,19 +112,12 @@ extern "C" int eab_energy_ratios_f32(const float* est, long long est_stride, int
                                      long long clean_stride, int clean_cap, const float* noisy, long long noisy_stride,
                                      int noisy_cap, const int32_t* lens, int B, double* partial, int partial_spans, double* out,
                                      eab_stream_t stream) {
-    EAB_CHECK_ARG(est && clean && noisy && lens && partial && out && B > 0 && B <= 65535);
-    EAB_CHECK_ARG(est_cap > 0 && clean_cap > 0 && noisy_cap > 0);
-    EAB_CHECK_ARG(est_cap <= SCORE_MAX_LEN && clean_cap <= SCORE_MAX_LEN && noisy_cap <= SCORE_MAX_LEN);
-    // rows of two utterances must not overlap (B = 1 has no second row)
-    EAB_CHECK_ARG(B == 1 || (est_stride >= est_cap && clean_stride >= clean_cap && noisy_stride >= noisy_cap));
+    const ScoreRows rows = {{est, clean, noisy}, {est_stride, clean_stride, noisy_stride}, {est_cap, clean_cap, noisy_cap}};
+    EAB_CHECK_ARG(lens && partial && out && eab_rows_ok(rows, B));
     int cap = est_cap > clean_cap ? est_cap : clean_cap;
     cap = cap > noisy_cap ? cap : noisy_cap;
     const int spans = (cap + SCORE_SPAN - 1) / SCORE_SPAN;
     EAB_CHECK_ARG(partial_spans >= spans);
-    ScoreRows rows;
-    rows.p[0] = est; rows.p[1] = clean; rows.p[2] = noisy;
-    rows.stride[0] = est_stride; rows.stride[1] = clean_stride; rows.stride[2] = noisy_stride;
-    rows.cap[0] = est_cap; rows.cap[1] = clean_cap; rows.cap[2] = noisy_cap;
     hipLaunchKernelGGL(energy_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(SCORE_THREADS), 0, eab_stream(stream), rows,
                        lens, partial_spans, partial);
     hipLaunchKernelGGL(energy_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, eab_stream(stream), partial, lens, rows, B,
@@ -158,24 +131,24 @@ __global__ __launch_bounds__(SCORE_THREADS) void loss_lens_partial_kernel(const 
                                                                           const int32_t* __restrict__ frames, int T_esti, int T_label,
                                                                           int T_max, int F, int spans, double* __restrict__ partial) {
     const int b = blockIdx.y, span = blockIdx.x;
-    const int len = score_clamp(frames[b], T_max) * F;
+    const int len = eab_clamp(frames[b], T_max) * F;
     if ((long long)span * SCORE_SPAN >= len) return;
     const long long pe = (long long)T_esti * F, pl = (long long)T_label * F;
     const float* er = esti + (long long)b * 2 * pe;
     const float* lr = label + (long long)b * 2 * pl;
     const float* ei = er + pe;
     const float* li = lr + pl;
-    const bool a0 = score_aligned(er), a1 = score_aligned(ei), a2 = score_aligned(lr), a3 = score_aligned(li);
+    const bool a0 = eab_aligned16(er), a1 = eab_aligned16(ei), a2 = eab_aligned16(lr), a3 = eab_aligned16(li);
     double acc[2] = {0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < SCORE_SPAN / (4 * SCORE_THREADS); ++j) {
         const int i = span * SCORE_SPAN + j * 4 * SCORE_THREADS + 4 * (int)threadIdx.x;
         if (i < len) {
             float v0[4], v1[4], v2[4], v3[4];
-            score_load4(er, a0, i, len, v0);
-            score_load4(ei, a1, i, len, v1);
-            score_load4(lr, a2, i, len, v2);
-            score_load4(li, a3, i, len, v3);
+            eab_load4(er, a0, i, len, v0);
+            eab_load4(ei, a1, i, len, v1);
+            eab_load4(lr, a2, i, len, v2);
+            eab_load4(li, a3, i, len, v3);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {                         // (bins at and past len are zeros: they add +0.0)
                 const float me = sqrtf(v0[k] * v0[k] + v1[k] * v1[k]), ml = sqrtf(v2[k] * v2[k] + v3[k] * v3[k]);
@@ -192,7 +165,7 @@ __global__ void loss_lens_final_kernel(const double* __restrict__ partial, const
                                        int spans, double* __restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int len = score_clamp(frames[b], T_max) * F;
+    const int len = eab_clamp(frames[b], T_max) * F;
     const int used = (len + SCORE_SPAN - 1) / SCORE_SPAN;
     double a = 0.0, c = 0.0;
     for (int k = 0; k < used; ++k) {
@@ -207,7 +180,7 @@ extern "C" int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* lab
                                              eab_stream_t stream) {
     EAB_CHECK_ARG(esti && label && frames && partial && loss && B > 0 && B <= 65535 && T_esti > 0 && T_label > 0 && F > 0);
     const int T_max = T_esti < T_label ? T_esti : T_label;
-    EAB_CHECK_ARG((long long)T_max * F <= SCORE_MAX_LEN);
+    EAB_CHECK_ARG((long long)T_max * F <= EAB_ROWS_MAX_LEN);
     const int spans = (T_max * F + SCORE_SPAN - 1) / SCORE_SPAN;
     EAB_CHECK_ARG(partial_spans >= spans);
     hipLaunchKernelGGL(loss_lens_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(SCORE_THREADS), 0, eab_stream(stream), esti,

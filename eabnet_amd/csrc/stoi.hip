@@ -24,7 +24,7 @@
 // samples at once, any other one by one AT THE SAME indices); no atomics.  An utterance has the same bits alone, in any batch
 // and in a second call.
 // Bound: launch latency; kernel 3 reads every kept sample twice (L2) and does ~25 kFLOP per frame.
-#include "common.h"
+#include "rows.h"
 #include "fft_lds.h"
 
 #define STOI_THREADS 256
@@ -37,17 +37,12 @@
 #define STOI_EFRAMES 16                       /* frames per workgroup of kernel 1 */
 #define STOI_TILE 16                          /* segments per workgroup of kernel 4 */
 #define STOI_TILE_FRAMES (STOI_TILE + STOI_SEG - 1)
-#define STOI_MAX_LEN (1 << 30)
 #define STOI_EPS 2.220446049250313e-16        /* 2^-52 */
 
 // band i sums the bins [stoi_edge[i], stoi_edge[i + 1])
 __device__ const int stoi_edge[STOI_BANDS + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
 
-struct StoiRows {
-    const float* p[2];            // clean, processed
-    long long stride[2];          // floats between the rows of two utterances
-    int cap[2];                   // floats of a row that may be read
-};
+typedef EabRows<2> StoiRows;        // clean, processed
 
 struct StoiWork {                 // byte offsets into the workspace
     size_t win, tw, energy, kept, K, tob, partial, total;
@@ -55,8 +50,6 @@ struct StoiWork {                 // byte offsets into the workspace
 
 static inline int stoi_frames_host(long long L) { return L > STOI_N ? (int)((L - STOI_N + STOI_HOP - 1) / STOI_HOP) : 0; }
 __device__ __forceinline__ int stoi_frames(int L) { return L > STOI_N ? (L - STOI_N + STOI_HOP - 1) / STOI_HOP : 0; }
-__device__ __forceinline__ int stoi_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-__device__ __forceinline__ bool stoi_aligned(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 static StoiWork stoi_layout(int B, int FC) {
     const size_t tiles = (size_t)(FC + STOI_TILE - 1) / STOI_TILE;
@@ -73,21 +66,10 @@ static StoiWork stoi_layout(int B, int FC) {
     return w;
 }
 
-// four consecutive samples of a row at index i (a multiple of four); zero at and past len
-__device__ __forceinline__ void stoi_load4(const float* __restrict__ row, bool aligned, int i, int len, float v[4]) {
-    if (aligned && i + 4 <= len) {
-        const f32x4 q = *reinterpret_cast<const f32x4*>(row + i);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = i + k < len ? row[i + k] : 0.0f;
-    }
-}
-
 // lens [B][2] = samples of (processed, clean): the order of the Python call's (est, clean)
 __device__ __forceinline__ void stoi_lens(const int32_t* __restrict__ lens, const StoiRows& rows, int b, int& ls, int& le) {
-    le = stoi_clamp(lens[2 * b], rows.cap[1]);
-    ls = stoi_clamp(lens[2 * b + 1], rows.cap[0]);
+    le = eab_clamp(lens[2 * b], rows.cap[1]);
+    ls = eab_clamp(lens[2 * b + 1], rows.cap[0]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -112,13 +94,13 @@ __global__ __launch_bounds__(STOI_THREADS) void stoi_energy_kernel(const StoiRow
     w[tid] = wv;
     __syncthreads();
     const float* x = rows.p[0] + (long long)b * rows.stride[0];
-    const bool al = stoi_aligned(x);
+    const bool al = eab_aligned16(x);
     const int lane = tid & 63, wave = tid >> 6;
     for (int f = wave; f < STOI_EFRAMES; f += STOI_THREADS / 64) {
         const int j = j0 + f;
         if (j >= NF) break;                                             // (wave-uniform)
         float v[4];
-        stoi_load4(x, al, STOI_HOP * j + 4 * lane, ls, v);
+        eab_load4(x, al, STOI_HOP * j + 4 * lane, ls, v);
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(STOI_THREADS) void stoi_bands_kernel(const StoiRows
     stoi_lens(lens, rows, b, ls, le);
     const int len = sig ? le : ls;
     const float* x = rows.p[sig] + (long long)b * rows.stride[sig];
-    const bool al = stoi_aligned(x);
+    const bool al = eab_aligned16(x);
     tw[tid] = tw_tab[tid];
     tw[tid + STOI_N] = tw_tab[tid + STOI_N];
     win[tid] = win_tab[tid];
@@ -206,9 +188,9 @@ __global__ __launch_bounds__(STOI_THREADS) void stoi_bands_kernel(const StoiRows
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (t0 + f < T) {                                               // (wave-uniform)
             float own[4], nb[4] = {0.f, 0.f, 0.f, 0.f};
-            stoi_load4(x, al, STOI_HOP * src[f + 1] + n, len, own);
+            eab_load4(x, al, STOI_HOP * src[f + 1] + n, len, own);
             const int other = n < STOI_HOP ? src[f] : src[f + 2], on = n < STOI_HOP ? n + STOI_HOP : n - STOI_HOP;
-            if (other >= 0) stoi_load4(x, al, STOI_HOP * other + on, len, nb);
+            if (other >= 0) eab_load4(x, al, STOI_HOP * other + on, len, nb);
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = (win[n + k] * own[k] + win[on + k] * nb[k]) * win[n + k];
         }
@@ -368,7 +350,7 @@ __global__ void stoi_final_kernel(int B, int tiles, const int32_t* __restrict__ 
 }
 
 extern "C" int eab_stoi_frame_capacity(int cap) {
-    if (cap <= 0 || cap > STOI_MAX_LEN) return -1;
+    if (cap <= 0 || cap > EAB_ROWS_MAX_LEN) return -1;
     const int f = stoi_frames_host(cap);
     return f > 0 ? f : 1;
 }
@@ -382,10 +364,8 @@ extern "C" long long eab_stoi_workspace_bytes(int B, int cap) {
 extern "C" int eab_stoi_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
                             int clean_cap, const int32_t* lens, int B, void* work, long long work_bytes, double* out,
                             int32_t* tap_K, int32_t* tap_kept, float* tap_tob, eab_stream_t stream) {
-    EAB_CHECK_ARG(est && clean && lens && work && out && B > 0 && B <= 65535);
-    EAB_CHECK_ARG(est_cap > 0 && clean_cap > 0 && est_cap <= STOI_MAX_LEN && clean_cap <= STOI_MAX_LEN);
-    // rows of two utterances must not overlap (B = 1 has no second row)
-    EAB_CHECK_ARG(B == 1 || (est_stride >= est_cap && clean_stride >= clean_cap));
+    const StoiRows rows = {{clean, est}, {clean_stride, est_stride}, {clean_cap, est_cap}};
+    EAB_CHECK_ARG(lens && work && out && eab_rows_ok(rows, B));
     EAB_CHECK_ARG((reinterpret_cast<uintptr_t>(work) & 15u) == 0);
     const int FC = eab_stoi_frame_capacity(est_cap > clean_cap ? est_cap : clean_cap);
     const StoiWork w = stoi_layout(B, FC);
@@ -399,10 +379,6 @@ extern "C" int eab_stoi_f32(const float* est, long long est_stride, int est_cap,
     int32_t* K = tap_K ? tap_K : reinterpret_cast<int32_t*>(base + w.K);
     float* tob = tap_tob ? tap_tob : reinterpret_cast<float*>(base + w.tob);
     double* partial = reinterpret_cast<double*>(base + w.partial);
-    StoiRows rows;
-    rows.p[0] = clean; rows.p[1] = est;
-    rows.stride[0] = clean_stride; rows.stride[1] = est_stride;
-    rows.cap[0] = clean_cap; rows.cap[1] = est_cap;
     hipStream_t s = eab_stream(stream);
     hipLaunchKernelGGL(stoi_energy_kernel, dim3((unsigned)((FC + STOI_EFRAMES - 1) / STOI_EFRAMES), (unsigned)B), dim3(STOI_THREADS), 0,
                        s, rows, lens, FC, energy, win, tw);

@@ -11,14 +11,7 @@
 //   w_dnn ReLU                   EaBNet.py:595
 //   filter-and-sum               EaBNet.py:114-117
 // All tensors channels-last [B][P][C] fp32 (P = T*F positions); roofline "hbm" for every kernel in this file.
-#include "common.h"
-
-// two fp32 -> packed bf16, round to nearest even (v_cvt_pk_bf16_f32): the rounding the bf16 contractions apply to their operands
-typedef __bf16 tr_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned tr_bf2(float x0, float x1) {
-    const tr_bf16x2 v = {(__bf16)x0, (__bf16)x1};
-    return __builtin_bit_cast(unsigned, v);
-}
+#include "device.h"
 
 #define TR_THREADS 256
 
@@ -254,7 +247,7 @@ __global__ __launch_bounds__(TR_THREADS) void tr_norm_act_kernel(const float* __
                 o[j] = MODE == EAB_XF_NORM_PRELU ? eab_prelu(fmaf(v[u][j], sc[j], sh[j]), sl[j]) : fmaf(eab_prelu(v[u][j], sl[j]), sc[j], sh[j]);
             if (add) o += ad[u];
             if (store_bf16)                       // the tensor is read by bf16 contractions only: store what they would round to
-                reinterpret_cast<uint2*>(y)[base + r] = make_uint2(tr_bf2(o[0], o[1]), tr_bf2(o[2], o[3]));
+                reinterpret_cast<uint2*>(y)[base + r] = make_uint2(eab_bf2(o[0], o[1]), eab_bf2(o[2], o[3]));
             else
                 reinterpret_cast<f32x4*>(y)[base + r] = o;
         }
@@ -461,7 +454,7 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_apply_kernel(const float*
                 }
                 if (acc_in) r += aq[u];
                 if (dx_bf16)                               // read by bf16 contractions only (wgrad, dgrad): half the bytes
-                    *reinterpret_cast<uint2*>(reinterpret_cast<char*>(dx) + e * 2) = make_uint2(tr_bf2(r[0], r[1]), tr_bf2(r[2], r[3]));
+                    *reinterpret_cast<uint2*>(reinterpret_cast<char*>(dx) + e * 2) = make_uint2(eab_bf2(r[0], r[1]), eab_bf2(r[2], r[3]));
                 else
                     *reinterpret_cast<f32x4*>(&dx[e]) = r;
             }
@@ -676,7 +669,7 @@ __global__ __launch_bounds__(TR_THREADS) void glu_bwd_kernel(const float* __rest
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = half[u] ? d[u][j] * ot[u][j] * me[u][j] * (1.0f - me[u][j]) : d[u][j] * ot[u][j];
             if (dz_bf16)
-                *reinterpret_cast<uint2*>(reinterpret_cast<char*>(dz) + at[u] * 2) = make_uint2(tr_bf2(o[0], o[1]), tr_bf2(o[2], o[3]));
+                *reinterpret_cast<uint2*>(reinterpret_cast<char*>(dz) + at[u] * 2) = make_uint2(eab_bf2(o[0], o[1]), eab_bf2(o[2], o[3]));
             else
                 *reinterpret_cast<f32x4*>(&dz[at[u]]) = o;
         }
@@ -913,13 +906,6 @@ extern "C" int eab_filter_sum_bwd_f32(const float* dout, const float* x, float* 
 // LayerNorm(64) over the channel axis of [rows][64] (EaBNet.py:598,608), forward with saved (mean, rstd), and
 // backward.  16 lanes x float4 per row (DPP row reductions); dgamma / dbeta through LDS + atomics.
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float tr_row_sum(float v) {      // sum over the 16 lanes of a DPP row
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
 
 __global__ __launch_bounds__(TR_THREADS) void layernorm_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                                    const float* __restrict__ b, float eps, float* __restrict__ y,
@@ -928,9 +914,9 @@ __global__ __launch_bounds__(TR_THREADS) void layernorm_fwd_kernel(const float* 
     const f32x4 g4 = *reinterpret_cast<const f32x4*>(g + lc), b4 = *reinterpret_cast<const f32x4*>(b + lc);
     for (long long r = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); r < rows; r += (long long)gridDim.x * 16) {
         f32x4 v = *reinterpret_cast<const f32x4*>(&x[r * 64 + lc]);
-        const float mean = tr_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
+        const float mean = eab_row_sum((v[0] + v[1]) + (v[2] + v[3])) * (1.0f / 64.0f);
         const f32x4 d = {v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
-        const float q = tr_row_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
+        const float q = eab_row_sum((d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]));
         const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + eps);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = d[j] * rstd * g4[j] + b4[j];
@@ -959,8 +945,8 @@ __global__ __launch_bounds__(TR_THREADS) void layernorm_bwd_kernel(const float* 
             sg[j] += d[j] * xh[j];
             sb[j] += d[j];
         }
-        const float A = tr_row_sum((dh[0] + dh[1]) + (dh[2] + dh[3])) * (1.0f / 64.0f);
-        const float Q = tr_row_sum((dh[0] * xh[0] + dh[1] * xh[1]) + (dh[2] * xh[2] + dh[3] * xh[3])) * (1.0f / 64.0f);
+        const float A = eab_row_sum((dh[0] + dh[1]) + (dh[2] + dh[3])) * (1.0f / 64.0f);
+        const float Q = eab_row_sum((dh[0] * xh[0] + dh[1] * xh[1]) + (dh[2] * xh[2] + dh[3] * xh[3])) * (1.0f / 64.0f);
         f32x4 o;
 #pragma unroll
         for (int j = 0; j < 4; ++j) o[j] = m.y * (dh[j] - A - xh[j] * Q);

@@ -12,7 +12,7 @@
 // Split-K over the rows: grid.x row groups accumulate into dW with fp32 atomics (dW zeroed by the caller).  The
 // column sums of dz (the bias gradient) ride along in the workgroups of column block 0 (dbias, optional).
 // Roofline "mfma" (fp32 dense, 157.3 TFLOP/s); algorithmic bytes = rows * (N + ntaps*C) * 4 per launch.
-#include "common.h"
+#include "device.h"
 #include <math.h>
 
 #define WG_THREADS 256
@@ -145,7 +145,6 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
         const_cast<float*>(m_src0), 0, (unsigned)((size_t)d.B * d.T * d.Fin * d.C0 * 4), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_s1 = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(m_src1 ? m_src1 : m_src0), 0, m_src1 ? (unsigned)((size_t)d.B * d.T * d.Fin * d.C1 * 4) : 0u, 0x00020000);
-    constexpr unsigned WG_OOB = 0x80000000u;
     WgRow ra_[AP], rb_;
     unsigned offA[AP];
     int offB[BP];                                                // (may be negative while the tap is out of range: unused then)
@@ -177,7 +176,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
 #pragma unroll
         for (int p = 0; p < AP; ++p) {
             const bool ok = r0 + a_row + 8 * p < r_end;
-            ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, ok ? offA[p] : WG_OOB, 0, 0));
+            ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, ok ? offA[p] : EAB_OOB, 0, 0));
             offA[p] += dA0 + (ra_[p].step(adv_a, adv_r, d.T, d.No) ? dA1 : 0u);
         }
         const bool rok = r0 + b_row < r_end;
@@ -185,7 +184,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
         for (int j = 0; j < BP; ++j) {
             const int tt = rb_.t + tdt[j], fi = rb_.o * d.istride + tio[j];
             const bool ok = rok && b_ok[j] && tt >= 0 && tt < d.T && fi >= 0 && fi < d.Fin;
-            const unsigned off = ok ? (unsigned)offB[j] : WG_OOB;
+            const unsigned off = ok ? (unsigned)offB[j] : EAB_OOB;
             if (vec_ok) {
                 rb[j] = __builtin_bit_cast(f32x4, b_second[j] ? __builtin_amdgcn_raw_buffer_load_b128(rs_s1, off, 0, 0)
                                                               : __builtin_amdgcn_raw_buffer_load_b128(rs_s0, off, 0, 0));
@@ -193,7 +192,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     rb[j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                             rs_s0, (ok && b_cc[j] + e < b_Cs[j]) ? off + 4u * e : WG_OOB, 0, 0));
+                                                             rs_s0, (ok && b_cc[j] + e < b_Cs[j]) ? off + 4u * e : EAB_OOB, 0, 0));
             }
         }
         const bool wrap = rb_.step(adv_a, adv_r, d.T, d.No);
@@ -286,16 +285,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
 // stride: the dword writes of a float4's four columns and the 4-dword fragment reads both spread over the banks): lane
 // (i, g) of the MFMA reads the dwords 4g..4g+3 of column i = its eight k values.  Thread -> row pair tid/32, float4 tid%32.
 // ---------------------------------------------------------------------------------------------------------------
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int wg_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int wg_u32x2 __attribute__((ext_vector_type(2)));
 #define WGB_S 9
-
-__device__ __forceinline__ unsigned wg_bf2(float x0, float x1) {
-    const wg_bf16x2 v = {(__bf16)x0, (__bf16)x1};
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // HALF (compile time, so that the operand loads of a stage stay one straight-line burst): bit 0 = dz, bit 1 = x stored as bf16
 template <int TN, int TC, int HALF, bool VEC>
@@ -353,7 +343,6 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
         const_cast<float*>(m_dz), 0, (unsigned)((size_t)d.B * d.T * d.Fz * d.N * eszA), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(b_src), 0, (unsigned)((size_t)d.B * d.T * d.Fin * b_Cs * eszB), 0x00020000);
-    constexpr unsigned WG_OOB = 0x80000000u;
     WgRow rw[2];
     unsigned offA[2];
     int offB[2];
@@ -375,24 +364,24 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
         for (int e = 0; e < 2; ++e) {
             const bool rok = r0 + 2 * rp + e < r_end;
             if (a_half) {                                         // (workgroup-uniform)
-                const wg_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_dz, (rok && a_live) ? offA[e] : WG_OOB, 0, 0);
-                ra[e] = __builtin_bit_cast(f32x4, wg_u32x4{v[0], v[1], 0u, 0u});
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_dz, (rok && a_live) ? offA[e] : EAB_OOB, 0, 0);
+                ra[e] = __builtin_bit_cast(f32x4, u32x4{v[0], v[1], 0u, 0u});
             } else {
-                ra[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, (rok && a_live) ? offA[e] : WG_OOB, 0, 0));
+                ra[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, (rok && a_live) ? offA[e] : EAB_OOB, 0, 0));
             }
             const int tt = rw[e].t + tdt, fi = rw[e].o * d.istride + tio;
             const bool ok = rok && b_ok && tt >= 0 && tt < d.T && fi >= 0 && fi < d.Fin;
-            const unsigned off = ok ? (unsigned)offB[e] : WG_OOB;
+            const unsigned off = ok ? (unsigned)offB[e] : EAB_OOB;
             if (b_half) {                                         // (uniform per thread's column block; C % 16 == 0: host check)
-                const wg_u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_src, off, 0, 0);
-                rb[e] = __builtin_bit_cast(f32x4, wg_u32x4{v[0], v[1], 0u, 0u});
+                const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_src, off, 0, 0);
+                rb[e] = __builtin_bit_cast(f32x4, u32x4{v[0], v[1], 0u, 0u});
             } else if (vec_ok) {
                 rb[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_src, off, 0, 0));
             } else {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     rb[e][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                             rs_src, (ok && b_cc + q < b_Cs) ? off + 4u * q : WG_OOB, 0, 0));
+                                                             rs_src, (ok && b_cc + q < b_Cs) ? off + 4u * q : EAB_OOB, 0, 0));
             }
             const bool wrap = rw[e].step(adv_a, adv_r, d.T, d.No);
             offA[e] += dA0 + (wrap ? dA1 : 0u);
@@ -403,14 +392,14 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
         // row pair -> one dword per column: (row 2rp, row 2rp+1) as (low, high) bf16
         auto pair4 = [](const f32x4 (&r)[2], bool half, unsigned (&o)[4]) {
             if (half) {                                           // r[e] = two dwords holding the row's four bf16
-                const wg_u32x4 r0 = __builtin_bit_cast(wg_u32x4, r[0]), r1 = __builtin_bit_cast(wg_u32x4, r[1]);
+                const u32x4 r0 = __builtin_bit_cast(u32x4, r[0]), r1 = __builtin_bit_cast(u32x4, r[1]);
                 o[0] = __builtin_amdgcn_perm(r1[0], r0[0], 0x05040100u);
                 o[1] = __builtin_amdgcn_perm(r1[0], r0[0], 0x07060302u);
                 o[2] = __builtin_amdgcn_perm(r1[1], r0[1], 0x05040100u);
                 o[3] = __builtin_amdgcn_perm(r1[1], r0[1], 0x07060302u);
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = wg_bf2(r[0][j], r[1][j]);
+                for (int j = 0; j < 4; ++j) o[j] = eab_bf2(r[0][j], r[1][j]);
             }
         };
         if (a_live) {
@@ -447,8 +436,8 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
     auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     const int a_off = (wm * (TN / 2) + li) * WGB_S + 4 * lh, b_off = (wn * (TC / 2) + li) * WGB_S + 4 * lh;
     auto frag = [](const unsigned* p) {
-        const wg_u32x4 v = {p[0], p[1], p[2], p[3]};
-        return __builtin_bit_cast(wg_bf16x8, v);
+        const u32x4 v = {p[0], p[1], p[2], p[3]};
+        return __builtin_bit_cast(bf16x8, v);
     };
 
     if (r_begin < r_end) {
@@ -459,7 +448,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
         for (long long r0 = r_begin; r0 < r_end; r0 += WG_ROWS) {
             const bool more = r0 + WG_ROWS < r_end;
             if (more) fetch(r0 + WG_ROWS);
-            wg_bf16x8 av[MI], bv[NJ];
+            bf16x8 av[MI], bv[NJ];
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) av[mi] = frag(&a_t[cur][a_off + mi * 32 * WGB_S]);
 #pragma unroll

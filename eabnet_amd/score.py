@@ -41,21 +41,27 @@ def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
-def _check_lens3(lengths, B: int, widths: Tuple[int, int, int]) -> list:
-    """the checked sample counts of (est, clean, noisy), each a list or a device tensor; None: the full rows"""
+def _check_lens(lengths, B: int, widths: Sequence[int], what: str) -> list:
+    """the checked sample counts of one signal per width (``what`` names them: "triple (est, clean, noisy)"), each a list or a
+    device tensor; None: the full rows"""
     if lengths is None:
         lengths = [[w] * B for w in widths]
     lengths = list(lengths)
-    if len(lengths) != 3:
-        raise ValueError(f"lengths must be a triple (est, clean, noisy) of (B,) counts, got {len(lengths)} members")
+    if len(lengths) != len(widths):
+        raise ValueError(f"lengths must be a {what} of (B,) counts, got {len(lengths)} members")
     return [_m.check_lengths(l, B, w, lo=1, unit="the signal's row length", integral=True) for l, w in zip(lengths, widths)]
 
 
-def _lens3(cols: list, B: int, device: torch.device) -> torch.Tensor:
-    """checked counts as the (B, 3) int32 device array of the kernel"""
+def _lens(cols: list, B: int, device: torch.device) -> torch.Tensor:
+    """checked counts as the (B, len(cols)) int32 device array of the kernels"""
     if not any(isinstance(c, torch.Tensor) for c in cols):
-        return _m._device_lengths([v for row in zip(*cols) for v in row], device).view(B, 3)
+        return _m._device_lengths([v for row in zip(*cols) for v in row], device).view(B, len(cols))
     return torch.stack([_m._device_lengths(c, device) for c in cols], dim=1).contiguous()
+
+
+def _row_args(B: int, *tensors: torch.Tensor) -> list:
+    """(pointer, floats between two rows, floats of a row that may be read) of every row tensor: EabRows of csrc/rows.h"""
+    return [a for t in tensors for a in (t.data_ptr(), t.stride(0) if B > 1 else t.shape[1], t.shape[1])]
 
 
 def energy_ratios(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, lengths=None, energies: bool = False) -> torch.Tensor:
@@ -75,21 +81,18 @@ def energy_ratios(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, l
     B = est.shape[0]
     if clean.shape[0] != B or noisy.shape[0] != B:
         raise ValueError(f"est, clean and noisy must hold the same number of rows, got {B}, {clean.shape[0]}, {noisy.shape[0]}")
-    cols = _check_lens3(lengths, B, (est.shape[1], clean.shape[1], noisy.shape[1]))
+    cols = _check_lens(lengths, B, (est.shape[1], clean.shape[1], noisy.shape[1]), "triple (est, clean, noisy)")
     est, clean, noisy = _rows(est, "est"), _rows(clean, "clean"), _rows(noisy, "noisy")
     if not (est.device == clean.device == noisy.device):
         raise ValueError("est, clean and noisy must be on one device")
     widths = (est.shape[1], clean.shape[1], noisy.shape[1])
     lib = _lib.load()
     with torch.cuda.device(est.device):
-        lens = _lens3(cols, B, est.device)
+        lens = _lens(cols, B, est.device)
         spans = _spans(max(widths))
         partial = torch.empty((B, spans, 6), dtype=torch.float64, device=est.device)
         out = torch.empty((B, 8), dtype=torch.float64, device=est.device)
-        args = []
-        for t in (est, clean, noisy):
-            args += [t.data_ptr(), t.stride(0) if B > 1 else t.shape[1], t.shape[1]]
-        _lib.check(lib.eab_energy_ratios_f32(*args, lens.data_ptr(), B, partial.data_ptr(), spans, out.data_ptr(),
+        _lib.check(lib.eab_energy_ratios_f32(*_row_args(B, est, clean, noisy), lens.data_ptr(), B, partial.data_ptr(), spans, out.data_ptr(),
                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_energy_ratios_f32")
     return out if energies else out[:, :4]
 
@@ -134,10 +137,7 @@ def _stoi_rows(est: torch.Tensor, clean: torch.Tensor, cols: list, taps: bool):
     if FC < 0 or nbytes < 0:
         raise ValueError(f"intelligibility takes at most 65535 rows of at most 2^30 samples, got {B} rows of {cap}")
     with torch.cuda.device(est.device):
-        if not any(isinstance(c, torch.Tensor) for c in cols):
-            lens = _m._device_lengths([v for row in zip(*cols) for v in row], est.device).view(B, 2)
-        else:
-            lens = torch.stack([_m._device_lengths(c, est.device) for c in cols], dim=1).contiguous()
+        lens = _lens(cols, B, est.device)
         work = torch.empty((nbytes,), dtype=torch.uint8, device=est.device)
         out = torch.empty((B, 2), dtype=torch.float64, device=est.device)
         tap = None
@@ -145,11 +145,8 @@ def _stoi_rows(est: torch.Tensor, clean: torch.Tensor, cols: list, taps: bool):
             tap = {"K": torch.zeros((B,), dtype=torch.int32, device=est.device),
                    "kept": torch.zeros((B, FC), dtype=torch.int32, device=est.device),
                    "tob": torch.zeros((B, 2, 15, FC), dtype=torch.float32, device=est.device)}
-        args = []
-        for t in (est, clean):
-            args += [t.data_ptr(), t.stride(0) if B > 1 else t.shape[1], t.shape[1]]
         ptrs = [tap[k].data_ptr() for k in ("K", "kept", "tob")] if taps else [None, None, None]
-        _lib.check(lib.eab_stoi_f32(*args, lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), *ptrs,
+        _lib.check(lib.eab_stoi_f32(*_row_args(B, est, clean), lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), *ptrs,
                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_stoi_f32")
     return (out, tap) if taps else out
 
@@ -176,13 +173,7 @@ def intelligibility(est: torch.Tensor, clean: torch.Tensor, lengths=None, sample
     B = est.shape[0]
     if clean.shape[0] != B:
         raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
-    widths = (est.shape[1], clean.shape[1])
-    if lengths is None:
-        lengths = [[w] * B for w in widths]
-    lengths = list(lengths)
-    if len(lengths) != 2:
-        raise ValueError(f"lengths must be a pair (est, clean) of (B,) counts, got {len(lengths)} members")
-    cols = [_m.check_lengths(l, B, w, lo=1, unit="the signal's row length", integral=True) for l, w in zip(lengths, widths)]
+    cols = _check_lens(lengths, B, (est.shape[1], clean.shape[1]), "pair (est, clean)")
     o, n = _rs._ratio(sample_rate, STOI_RATE)
     if not (est.is_cuda and clean.is_cuda):
         raise _lib.EabError("intelligibility needs CUDA (ROCm) tensors; there is no CPU fallback by design.")

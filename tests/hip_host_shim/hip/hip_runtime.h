@@ -1,4 +1,4 @@
-// Host stand-in for <hip/hip_runtime.h>, enough to run csrc/stoi.hip on the CPU (tests/test_stoi_host_emulation.py): one
+// Host stand-in for <hip/hip_runtime.h>, enough to run csrc/stoi.hip and csrc/score.hip on the CPU (tests/test_*_host_emulation.py): one
 // std::thread per lane of a workgroup, workgroups one after the other, __syncthreads and the wave operations through pthread
 // barriers.  Valid for kernels whose returns are workgroup-uniform and whose wave operations sit in wave-uniform control flow.
 // __shared__ becomes a function-local static: correct because only one workgroup runs at a time.

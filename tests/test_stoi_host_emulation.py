@@ -34,7 +34,8 @@ def program(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("stoi_emulation") / "stoi_emulation")
     cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"),
-           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "stoi.hip"), os.path.join(SHIM, "stoi_main.cpp"), "-o", exe, "-lpthread"]
+           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "stoi.hip"), os.path.join(SHIM, "shim.cpp"),
+           os.path.join(SHIM, "stoi_main.cpp"), "-o", exe, "-lpthread"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
     return exe
