@@ -244,6 +244,36 @@ int eab_resample_f32(const float* x, long long x_row_stride, int x_cols, const i
                      int n, int K, long long in_origin, long long out_origin, long long valid_hi, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Training mixtures of a padded batch: shoebox image-source rooms (csrc/room.hip).  Replaces, one sample at a time on the
+ * host, McseDatasetOnline (mcse_dataset.py:262-289 -> audio_util.py:6-88, rir_method "ism") by the definition of DESIGN.md
+ * §4.18 (the definition is the contract; equality with pyroomacoustics is not verified).  Only entry points are added:
+ * EAB_ABI_VERSION stays 10.
+ *
+ *   x       sources [B][S_max][L] fp32; row s >= S_b and samples >= lens[b] are never read
+ *   lens    DEVICE int32 [B], clamped to [0, L];  klen DEVICE int32 [B][2]: samples of utterance b's own responses, clamped to
+ *           [0, K], and the first sample anything can reach a microphone at (the output is exactly zero before it)
+ *   scenes  DEVICE double [B][144]: [0..2] room, [3] energy absorption, [4] order (<= 255), [5] S_b, [6] reference microphone,
+ *           [7] dBFS, [8 + j] snr_j, [16 + 3 s + axis] source s, [40 + 3 m + axis] microphone m; integers are clamped to
+ *           their ranges, so the kernels stay in bounds for any content
+ *   fs      sample rate of the whole batch; the active-rms window is int(fs / 10) samples
+ * eab_room_gains_f32: gains [B][S_max] double, the dry gains of mix_scaler (zeros for s >= S_b); partial is scratch of
+ *   partial_windows >= ceil(L / int(fs/10)) rows of 44 doubles per utterance.  Two launches, fp64 sums in one fixed order.
+ * eab_room_rirs_f32: h [B][S_max][M+1][K] fp32, row M the free-field response of the reference microphone (zeros for
+ *   s >= S_b).  Geometry in fp64, taps in fp32, summed as rint(tap * 2^40) in 64-bit integers: bits independent of scheduling.
+ *   A pulse is cut at K.  One launch.
+ * eab_room_convolve_f32: noisy [B][M][L] = sum_s gains[s] (x_s * h[s][m]), clean [B][L] = gains[0] (x_0 * h[0][M]), zero from
+ *   lens[b] on.  twiddle: DEVICE float [1024][2], exp(-2 pi i j / 1024); work: eab_room_workspace_bytes bytes, 16-byte
+ *   aligned.  Three launches; an utterance has the same bits alone, in any batch and in a second call.
+ * ------------------------------------------------------------------------ */
+int eab_room_gains_f32(const float* x, int B, int S_max, int L, const int32_t* lens, const double* scenes, double fs,
+                       double* partial, int partial_windows, double* gains, eab_stream_t stream);
+int eab_room_rirs_f32(const double* scenes, int B, int S_max, int M, int K, double fs, float* h, eab_stream_t stream);
+long long eab_room_workspace_bytes(int B, int S_max, int M, int L, int K);
+int eab_room_convolve_f32(const float* x, int B, int S_max, int L, const int32_t* lens, const double* scenes, const int32_t* klen,
+                          const double* gains, const float* h, int M, int K, const float* twiddle, void* work,
+                          long long work_bytes, float* noisy, float* clean, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * K13  complex filter-and-sum, stand-alone.   Replaces EaBNet.py:114-117.
  *   w, x [B][T][F][M][2] -> y [B][2][T][F];  Y = sum_m W_m * X_m (no conjugate)
  * ------------------------------------------------------------------------ */
