@@ -41,7 +41,7 @@
 
 #define CG_PMAX 352  // input positions of one patch (PATCH mode): 352 * 80 B = 27.5 KB, three workgroups per CU
 
-template <int MI, int NI, int KU, int MODE, bool PATCH>
+template <int MI, int NI, int KU, int MODE, bool PATCH, bool XFT>
 struct CgSmem {
     static constexpr int BM = 64 * MI, BN = 64 * NI, LDK = 16 * KU + 4;
     static constexpr int NA = MODE == CG_DUAL ? 2 : 1;
@@ -55,6 +55,12 @@ struct CgSmem {
     int dt[EAB_MAX_TAPS];
     int ioff[EAB_MAX_TAPS];
     int last;                    // fused finalisation: this workgroup wrote the last partial of its batch element
+    // the epilogue's row table (one word per tile row, two in the phase-pair form): a launch without a fused transform
+    // (XFT false) keeps it in the unused transform tables, so the gated 128x128 tiles' LDS -- three workgroups per CU --
+    // stays what it was
+    static constexpr int RW = MODE == CG_PH2 ? 2 : 1;
+    __attribute__((aligned(16))) unsigned rtab_own[XFT ? BM * RW : 4];
+    static_assert(XFT || sizeof(float) * 2 * CG_XFC * 2 >= sizeof(unsigned) * BM * RW, "row table inside xft");
 };
 
 // Welford/Chan merge of two partial (count, mean, M2) statistics; (0,*,*) is the neutral element.  Not st_merge (conv_st.hip):
@@ -84,7 +90,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     constexpr bool PH2 = MODE == CG_PH2;            // (phase 0, phase 1) column pair per lane; own epilogue
     constexpr bool GLU = MODE != CG_PLAIN;          // paired columns per lane: gated epilogue (value tile, gate tile) / phase pair
     constexpr bool DUAL = MODE == CG_DUAL;
-    using Smem = CgSmem<MI, NI, KU, MODE, PATCH>;
+    using Smem = CgSmem<MI, NI, KU, MODE, PATCH, XF != EAB_XF_NONE>;
     constexpr int BM = Smem::BM, BN = Smem::BN, LDK = Smem::LDK;
     __shared__ __attribute__((aligned(16))) Smem sm;
 
@@ -123,6 +129,28 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             sm.dt[j] = d.dt[j];
             sm.ioff[j] = d.ioff[j];
         }
+
+    // Row table: where row q0 + i of the tile goes, said ONCE per tile by thread i instead of walked by every lane for each of
+    // its 16*MI rows in the epilogue: the byte offset of out[t][o*ostride + ophase][0] inside the batch element -- one
+    // division --, or EAB_OOB for a row past Q (a store there is dropped, a load gives 0; adding a lane's channel bytes
+    // keeps it out of range, the span of a batch element being below 2^31).  The phase-pair form keeps a second word per
+    // row: the offset one channel row on where column 2o+1 exists, EAB_OOB where it does not (the last o of a frame with
+    // an odd Fout).  Written here, before the barrier every kernel starts with, the table costs the epilogue no barrier of
+    // its own; its loops read a lane's four consecutive rows with one or two 16-byte LDS reads.
+    const int Cout = d.Cout;
+    const unsigned row_bytes = (unsigned)(d.Fout * Cout) * 4u, step_bytes = (unsigned)(d.ostride * Cout) * 4u;
+    const unsigned phase_bytes = (unsigned)(d.ophase * Cout) * 4u, chan_bytes = (unsigned)Cout * 4u;
+    unsigned* const rtab = XF != EAB_XF_NONE ? sm.rtab_own : reinterpret_cast<unsigned*>(&sm.xft[0][0][0]);
+    if (tid < BM) {
+        const int q = q0 + tid;
+        const bool ok = q < Q;
+        const int t = eab_div(ok ? q : 0, d.No, inv_no), o = (ok ? q : 0) - t * d.No;
+        const unsigned off = ok ? (unsigned)t * row_bytes + (unsigned)o * step_bytes + phase_bytes : EAB_OOB;
+        if constexpr (PH2)
+            *reinterpret_cast<uint2*>(&rtab[2 * tid]) = make_uint2(off, (ok && 2 * o + 1 < d.Fout) ? off + chan_bytes : EAB_OOB);
+        else
+            rtab[tid] = off;
+    }
 
     if (XF != EAB_XF_NONE) {
         // (scale, shift, slope) tables of this batch element -> LDS.  Either the host ran
@@ -194,18 +222,6 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     // ---- per-thread staging coordinates ------------------------------------------
     const int srow = tid >> 2;      // 0..63
     const int skq = tid & 3;        // which float4 of a 16-wide unit
-    int a_t[MI], a_f0[MI], a_tf[MI];
-    bool a_ok[MI];
-#pragma unroll
-    for (int p = 0; p < MI; ++p) {
-        const int q = q0 + srow + 64 * p;
-        a_ok[p] = q < Q;
-        const int t = a_ok[p] ? eab_div(q, d.No, inv_no) : 0;
-        const int o = a_ok[p] ? q - t * d.No : 0;
-        a_t[p] = t;
-        a_f0[p] = o * d.istride;
-        a_tf[p] = t * d.Fin + o * d.istride;
-    }
     const float* wrow[NI];
 #pragma unroll
     for (int p = 0; p < NI; ++p) wrow[p] = d.w + (size_t)(n_blk + srow + 64 * p) * d.Kpad + skq * 4;
@@ -254,15 +270,35 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         const int t_last = eab_div((q0 + BM < Q ? q0 + BM : (Q > q0 ? Q : q0 + 1)) - 1, d.No, inv_no);
         const int P = (t_last - t_first + 1 - dt_min) * Fp;          // <= CG_PMAX (checked on the host)
 
+        // Patch row pidx = srow + 64*pp of pass pp is (t_in, f) = divmod(pidx, Fp): one division per thread, then a step of 64
+        // positions per pass -- 64 = d64*Fp + m64 (workgroup-uniform), one wrap test.  A pass with 64*pp >= P (workgroup-uniform)
+        // holds no position any fragment reads: it is neither fetched nor transformed nor stashed, its entries stay unset.
+        const int d64 = eab_div(64, Fp, inv_fp), m64 = 64 - d64 * Fp;
         int p_tf[PP];
-        bool p_ok[PP];
+        bool p_ok[PP], p_all[PP];
+        {
+            const int tr = eab_div(srow, Fp, inv_fp);
+            int f = srow - tr * Fp, t_in = t_first + dt_min + tr;
+            int tf = t_in * d.Fin + f - halo_lo;
 #pragma unroll
-        for (int pp = 0; pp < PP; ++pp) {
-            const int pidx = srow + 64 * pp;
-            const int tr = eab_div(pidx, Fp, inv_fp);
-            const int t_in = t_first + dt_min + tr, fi = pidx - tr * Fp - halo_lo;
-            p_ok[pp] = pidx < P && t_in >= 0 && t_in < d.T && fi >= 0 && fi < d.Fin;
-            p_tf[pp] = t_in * d.Fin + fi;
+            for (int pp = 0; pp < PP; ++pp) {
+                p_ok[pp] = p_all[pp] = false;
+                p_tf[pp] = 0;
+                if (64 * pp < P) {
+                    p_ok[pp] = srow + 64 * pp < P && (unsigned)t_in < (unsigned)d.T && (unsigned)(f - halo_lo) < (unsigned)d.Fin;
+                    // every position of this wave's sixteen real: the fused transform needs no zero-select in this pass
+                    if (XF != EAB_XF_NONE) p_all[pp] = __builtin_amdgcn_ballot_w64(p_ok[pp]) == __builtin_amdgcn_ballot_w64(true);
+                    p_tf[pp] = tf;
+                    f += m64;
+                    t_in += d64;
+                    tf += d64 * d.Fin + m64;
+                    if (f >= Fp) {
+                        f -= Fp;
+                        ++t_in;
+                        tf += d.Fin - Fp;
+                    }
+                }
+            }
         }
         int fa[MI];                                                  // float index of this lane's fragment for a zero tap shift
 #pragma unroll
@@ -286,6 +322,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             p_tc = ((second ? 1 : 0) << 8) | (cok ? c : 0);
 #pragma unroll
             for (int pp = 0; pp < PP; ++pp) {
+                if (64 * pp >= P) continue;                          // dead pass (workgroup-uniform)
                 const unsigned off = (p_ok[pp] && cok) ? (unsigned)((p_tf[pp] * Cs + c) * 4) : EAB_OOB;
                 const u32x4 v = second ? __builtin_amdgcn_raw_buffer_load_b128(rs1, off, 0, 0)
                                        : __builtin_amdgcn_raw_buffer_load_b128(rs0, off, 0, 0);
@@ -304,10 +341,15 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             for (int pp = 0; pp < PP; ++pp) {
                 const int pidx = srow + 64 * pp;
                 if (pidx >= CG_PMAX) continue;
+                if (64 * pp >= P) continue;                          // dead pass (workgroup-uniform)
                 f32x4 v = rp[pp];
                 if (XF != EAB_XF_NONE) {
                     const f32x4 x = eab_xform<XF>(v, sh01, sh23, sl);
-                    v = p_ok[pp] ? x : f32x4{0.f, 0.f, 0.f, 0.f};     // halo / causal zeros stay exactly 0
+                    v = x;
+                    if (!p_all[pp]) {                                 // (wave-uniform) halo / causal zeros stay exactly 0
+                        asm volatile("; rim" ::: "memory");
+                        v = p_ok[pp] ? x : f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
                 }
                 float* arow = &sm.a[pidx * LDK];
                 if (BF) {
@@ -438,6 +480,18 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     // the transposed conv's implicit zeros come after norm+PReLU), so out-of-range
     // taps must stay exactly 0 through the fused transform: st_ok remembers which
     // staged rows are real.
+    int a_t[MI], a_f0[MI], a_tf[MI];   // output row (t, o) of each staged row: the gather pipeline's own (a patch has none)
+    bool a_ok[MI];
+#pragma unroll
+    for (int p = 0; p < MI; ++p) {
+        const int q = q0 + srow + 64 * p;
+        a_ok[p] = q < Q;
+        const int t = a_ok[p] ? eab_div(q, d.No, inv_no) : 0;
+        const int o = a_ok[p] ? q - t * d.No : 0;
+        a_t[p] = t;
+        a_f0[p] = o * d.istride;
+        a_tf[p] = t * d.Fin + o * d.istride;
+    }
     struct Stage {                  // one pipeline stage in flight in registers
         f32x4 ra[KU][MI], rb[KU][NI];
         f32x4 rb2[BF ? NI : 1];     // wide stages (bf16-stored source): the second four weights of the thread's eight
@@ -795,9 +849,11 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     }   // q0 < Q
 
     // ---- epilogue ---------------------------------------------------------------
+    // a lane's rows (mi, 4*r4 + j), j = 0..3, are tile rows rrow + 32*mi + 8*r4 + j
+    const int rrow = wm * MI * 32 + 4 * lh;
+
     // C/D map of the 32x32 MFMA: column = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
     constexpr int NC = GLU ? 1 : NI;            // output-channel groups of 32 held by this lane
-    const int Cout = d.Cout;
     int ch[NC];
     float bias_v[NI];
 #pragma unroll
@@ -842,8 +898,6 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     const __amdgpu_buffer_rsrc_t r_acc = __builtin_amdgcn_make_buffer_rsrc(
         d.dst_acc ? d.dst_acc + out_b : d.dst + out_b, 0, d.dst_acc ? out_bytes : 0u, 0x00020000);
 
-    const unsigned row_bytes = (unsigned)(d.Fout * Cout) * 4u, step_bytes = (unsigned)(d.ostride * Cout) * 4u;
-    const unsigned phase_bytes = (unsigned)(d.ophase * Cout) * 4u;
     if constexpr (PH2) {
         // ---- phase-pair epilogue (EAB_EPI_PHASE2): row q = (t, o) of the tile owns out[t][2o] (accumulator block 0) and
         // out[t][2o+1] (block 1; it exists while 2o+1 < Fout, i.e. not for the last o of a frame when Fout is odd).  Both
@@ -852,47 +906,51 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         // gives the same (mean, M2)).  Straight-line code; FULL = no row of the tile lies past the end.
         const float a = st_slope[0][0];
         const float k0 = eab_prelu(acc[0][0][0] + bias_v[0], a);
-        const unsigned chan_bytes = (unsigned)Cout * 4u;
-        float su = 0.0f, sq = 0.0f, cnt = 0.0f;
-        auto ph2_loop = [&](auto full_c) {
-            constexpr bool FULL = decltype(full_c)::value;
+        float su = 0.0f, sq = 0.0f;
+        int n1 = 0;                                 // existing elements this lane saw, where the tile does not fix the count
+        const unsigned chb = 4u * ch[0];
+        // ALL1 (workgroup-uniform, full tiles only): every row of the tile has its column 2o+1 -- Fout is even --, so neither
+        // the second offset nor any mask is read
+        auto ph2_loop = [&](auto full_c, auto all1_c) {
+            constexpr bool FULL = decltype(full_c)::value, ALL1 = decltype(all1_c)::value;
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
-                    const int qg = q0 + (wm * MI + mi) * 32 + 8 * r4 + 4 * lh;     // rows 4*r4 + j, j = 0..3: consecutive q
-                    const int t = eab_div((FULL || qg < Q) ? qg : 0, d.No, inv_no);
-                    int o = ((FULL || qg < Q) ? qg : 0) - t * d.No;
-                    unsigned row_start = (unsigned)t * row_bytes;
-                    unsigned cur = row_start + (unsigned)o * step_bytes;            // byte offset of out[t][2o][0]
+                    // rows 4*r4 + j, j = 0..3: (offset of the phase-0 store, offset of the phase-1 store) each, EAB_OOB = none
+                    const unsigned* row = &rtab[2 * (rrow + 32 * mi + 8 * r4)];
+                    const u32x4 e[2] = {*reinterpret_cast<const u32x4*>(row), *reinterpret_cast<const u32x4*>(row + 4)};
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int r = 4 * r4 + j;
-                        const bool ok0 = FULL || qg + j < Q;
-                        const bool ok1 = ok0 && 2 * o + 1 < d.Fout;
+                        const unsigned t0 = e[j >> 1][2 * (j & 1)], t1 = e[j >> 1][2 * (j & 1) + 1];
+                        const bool ok0 = FULL || (int)t0 >= 0;
+                        const bool ok1 = ALL1 || (int)t1 >= 0;
                         const float v0 = acc[mi][0][r] + bias_v[0], v1 = acc[mi][1][r] + bias_v[1];
-                        const unsigned o0 = cur + 4u * ch[0];
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), r_dst, ok0 ? o0 : EAB_OOB, 0, 0);
-                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), r_dst, ok1 ? o0 + chan_bytes : EAB_OOB, 0, 0);
+                        const unsigned o0 = t0 + chb;
+                        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), r_dst, o0, 0, 0);
+                        // every phase-1 column there: the neighbouring channel row through the scalar offset, no second add
+                        if (ALL1) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), r_dst, o0, chan_bytes, 0);
+                        else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), r_dst, t1 + chb, 0, 0);
                         const float e0 = eab_prelu(v0, a) - k0, e1 = eab_prelu(v1, a) - k0;
-                        const float m0 = FULL ? e0 : (ok0 ? e0 : 0.0f), m1 = ok1 ? e1 : 0.0f;
+                        const float m0 = FULL ? e0 : (ok0 ? e0 : 0.0f), m1 = ALL1 ? e1 : (ok1 ? e1 : 0.0f);
                         su += m0;
                         sq = fmaf(m0, m0, sq);
                         su += m1;
                         sq = fmaf(m1, m1, sq);
-                        cnt += (FULL ? 1.0f : (ok0 ? 1.0f : 0.0f)) + (ok1 ? 1.0f : 0.0f);
-                        cur += step_bytes;
-                        if (++o == d.No) {
-                            o = 0;
-                            row_start += row_bytes;
-                            cur = row_start;
-                        }
+                        if (!FULL) n1 += ok0 ? 1 : 0;
+                        if (!ALL1) n1 += ok1 ? 1 : 0;
                     }
                 }
             }
         };
-        if (q0 + BM <= Q) ph2_loop(std::true_type{});
-        else ph2_loop(std::false_type{});
+        const bool full = q0 + BM <= Q;
+        const bool all1 = full && d.Fout == 2 * d.No;
+        if (all1) ph2_loop(std::true_type{}, std::true_type{});
+        else if (full) ph2_loop(std::true_type{}, std::false_type{});
+        else ph2_loop(std::false_type{}, std::false_type{});
+        // the count is a fact of the tile: 16*MI rows per lane of a full tile, as many phase-1 columns where all exist
+        const float cnt = (float)((full ? 16 * MI : 0) + (all1 ? 16 * MI : 0) + n1);
         skk[0][0] = k0;
         ssum[0][0] = su;
         ssq[0][0] = sq;
@@ -914,21 +972,9 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                 unsigned off[16];
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
-                    const int qg = q0 + (wm * MI + mi) * 32 + 8 * r4 + 4 * lh;
-                    const int t = eab_div(qg, d.No, inv_no);
-                    int o = qg - t * d.No;
-                    unsigned row_start = (unsigned)t * row_bytes + phase_bytes;
-                    unsigned cur = row_start + (unsigned)o * step_bytes;
+                    const u32x4 e = *reinterpret_cast<const u32x4*>(&rtab[rrow + 32 * mi + 8 * r4]);
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        off[4 * r4 + j] = cur;
-                        cur += step_bytes;
-                        if (++o == d.No) {
-                            o = 0;
-                            row_start += row_bytes;
-                            cur = row_start;
-                        }
-                    }
+                    for (int j = 0; j < 4; ++j) off[4 * r4 + j] = e[j];
                 }
                 float auxv[16][NC];
                 if (ADDV) {
@@ -992,25 +1038,11 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         bool rowok[16];
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-            // rows r = 4*r4 + j, j = 0..3 are consecutive q: one division per group of four
-            const int qg = q0 + (wm * MI + mi) * 32 + 8 * r4 + 4 * lh;
-            const int t = eab_div(qg < Q ? qg : 0, d.No, inv_no);
-            int o = (qg < Q ? qg : 0) - t * d.No;
-            // byte offset of (t, o) stepped incrementally: two integer multiplies per group of four rows
-            // instead of three per row (v_mul_lo_u32 is quarter rate and shares the pipe with the fp32 MFMA)
-            unsigned row_start = (unsigned)t * row_bytes + phase_bytes;
-            unsigned cur = row_start + (unsigned)o * step_bytes;
+            const u32x4 e = *reinterpret_cast<const u32x4*>(&rtab[rrow + 32 * mi + 8 * r4]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const int r = 4 * r4 + j;
-                rowok[r] = qg + j < Q;
-                off[r] = rowok[r] ? cur : EAB_OOB;
-                cur += step_bytes;
-                if (++o == d.No) {
-                    o = 0;
-                    row_start += row_bytes;
-                    cur = row_start;
-                }
+                off[4 * r4 + j] = e[j];                       // EAB_OOB for a row past Q, and still out of range with a channel added
+                rowok[4 * r4 + j] = (int)e[j] >= 0;
             }
         }
         float auxv[16][NC], accv[16][NC];
@@ -1020,7 +1052,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     auxv[r][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                               r_aux, rowok[r] ? off[r] + 4u * ch[c] : EAB_OOB, 0, 0));
+                                                               r_aux, off[r] + 4u * ch[c], 0, 0));
         }
         if (d.dst_acc) {
 #pragma unroll
@@ -1028,7 +1060,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int c = 0; c < NC; ++c)
                     accv[r][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                               r_acc, rowok[r] ? off[r] + 4u * ch[c] : EAB_OOB, 0, 0));
+                                                               r_acc, off[r] + 4u * ch[c], 0, 0));
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1050,7 +1082,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                 if (d.epi == EAB_EPI_RELU) v = fmaxf(v, 0.0f);
                 else if (d.epi == EAB_EPI_MULSIG) v = auxv[r][c] * eab_fast_sigmoid(v);
                 else if (d.epi == EAB_EPI_ADD) v = v + auxv[r][c];
-                const unsigned o4 = rowok[r] ? off[r] + 4u * ch[c] : EAB_OOB;
+                const unsigned o4 = off[r] + 4u * ch[c];
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r_dst, o4, 0, 0);
                 if (d.dst_acc)
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v + accv[r][c]), r_acc, o4, 0, 0);
