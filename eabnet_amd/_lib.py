@@ -76,6 +76,11 @@ class ShiftDesc(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("row_floats", C.c_int32), ("rows", C.c_int32)]
 
 
+class OptimSegment(C.Structure):
+    """mirror of eab_optim_segment: one piece of the run of elements that eab_grad_sumsq_f64 / eab_adam_clip_f32 work on"""
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("n", C.c_longlong)]
+
+
 class EabError(RuntimeError):
     pass
 
@@ -114,6 +119,9 @@ _SIGS = {
     "eab_room_workspace_bytes": (C.c_longlong, [C.c_int] * 5),
     "eab_room_convolve_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 2
                               + [C.c_longlong] + [C.c_void_p] * 3),
+    "eab_grad_sumsq_f64": (C.c_int, [C.POINTER(OptimSegment), C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "eab_adam_clip_f32": (C.c_int, [C.POINTER(OptimSegment), C.c_int, C.c_void_p, C.c_longlong] + [C.c_double] * 7
+                          + [C.c_void_p, C.c_void_p]),
     "eab_gag_pack_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [TimeWindow, C.c_void_p]),
     "eab_gag_crm_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [TimeWindow, C.c_void_p]),
     "eab_gag_crm_bwd_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_void_p]),

@@ -309,7 +309,7 @@ class _HipModule(nn.Module):
         """Change detector for the packed weights (runs on every forward).  Every parameter / buffer slot
         contributes (storage address, version counter): in-place updates bump the version, ``.data =``
         re-assignment, a device move or ``load_state_dict(assign=True)`` change the address or the object in the
-        slot.  The slot list (owning module, name) is cached -- walking the ~800-node module tree costs more
+        slot; a kernel that writes parameters through raw addresses bumps the versions itself (FlatAdam.step).  The slot list (owning module, name) is cached -- walking the ~800-node module tree costs more
         than the rest of the host side of a step; looking the ~500 slots up does not."""
         slots = self.__dict__.get("_slot_list")
         if slots is None:

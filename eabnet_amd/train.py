@@ -979,6 +979,7 @@ class TrainBound(BoundProgram):
         self.inv = torch.from_numpy(prog.inv).to(device)
         self.serial = 0                     # forward passes run so far: a backward must belong to the latest one
         self.use_graph = True
+        self.flat_param_hits = 0            # forward passes that read the parameters from one flat buffer (no torch.cat)
 
     def update_bn_buffers(self, module, momentum: float = 0.1) -> None:
         """nn.BatchNorm's train-mode side effect (NormSwitch BN branch, EaBNet.py:677-681): running_mean / running_var move
@@ -1022,9 +1023,13 @@ class TrainFn(torch.autograd.Function):
         prog = bound.prog
         ctx.sync_group = sync_group
         st = torch.cuda.current_stream().cuda_stream
-        flat = torch.cat([p.detach().reshape(-1) for p in params])      # (one batched copy; fp32 parameters)
-        if flat.dtype != torch.float32:
-            flat = flat.to(torch.float32)
+        flat = flat_parameter_view(params)                              # FlatAdam's buffer: nothing to copy
+        if flat is not None:
+            bound.flat_param_hits += 1
+        else:
+            flat = torch.cat([p.detach().reshape(-1) for p in params])  # (one batched copy; fp32 parameters)
+            if flat.dtype != torch.float32:
+                flat = flat.to(torch.float32)
         bound.pack(flat, st)
         bound.serial += 1
         ctx.serial = bound.serial
@@ -1066,6 +1071,22 @@ class TrainFn(torch.autograd.Function):
         bound.unpack_grads(gflat, st)
         grads = finish_flat_gradient(gflat, ctx.sync_group, ctx.shapes, ctx.dtypes, ctx.needs_input_grad[3:])
         return (None, None, None, *grads)
+
+
+def flat_parameter_view(params) -> Optional[torch.Tensor]:
+    """The 1-D fp32 tensor that ``params`` are consecutive contiguous slices of, in order (what eabnet_amd.FlatAdam leaves
+    behind), or None.  Exact: every parameter is checked for its address, dtype and contiguity, and the run for lying inside
+    the first parameter's storage (addresses are unique across devices)."""
+    first, f32 = params[0], torch.float32
+    nxt = start = first.data_ptr()
+    for p in params:
+        if p.data_ptr() != nxt or p.dtype is not f32 or not p.is_contiguous():
+            return None
+        nxt += 4 * p.numel()
+    store = first.untyped_storage()
+    if start < store.data_ptr() or nxt > store.data_ptr() + store.nbytes():
+        return None
+    return torch.as_strided(first.detach(), ((nxt - start) // 4,), (1,))
 
 
 def finish_flat_gradient(gflat: torch.Tensor, sync_group, shapes, dtypes, needs) -> list:

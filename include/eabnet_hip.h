@@ -274,6 +274,42 @@ int eab_room_convolve_f32(const float* x, int B, int S_max, int L, const int32_t
                           long long work_bytes, float* noisy, float* clean, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * The end of the training step on flat buffers (csrc/optim.hip): global gradient norm, clip_grad_norm_ and torch.optim.Adam
+ * (no amsgrad, maximize False) of train_distributed.py:222-230, two launches.  DESIGN.md §4.19 has the definition and the
+ * bounds.  Only entry points are added: EAB_ABI_VERSION stays 10.
+ *
+ * A segment table (host memory, 1 .. EAB_OPTIM_MAX_SEGMENTS entries) describes ONE run of elements: the segments laid end to
+ * end.  Chunk k is the elements [k, k + 1) * EAB_OPTIM_CHUNK of that run, whichever segments they lie in, so the chunk
+ * boundaries depend on the values' positions in the run alone and not on how the run is cut into segments.  n = 0 is allowed.
+ * eab_grad_sumsq_f64: reads grad and n of every segment; partial[k] = sum of squares of chunk k in fp64 (lane t of 256 owns
+ *   the elements 4t + 1024 j + {0..3} of the chunk in that order, lanes by a fixed shuffle tree, waves in index order); a
+ *   16-byte aligned piece loads four values at once, any other one by one AT THE SAME indices.  No atomics: the same bits in
+ *   every run and for every segmentation.  partial_cap >= ceil(sum n / EAB_OPTIM_CHUNK).  One launch (none for sum n = 0).
+ * eab_adam_clip_f32: every workgroup adds partial[0 .. npartial) in one fixed order (lane t the entries t + 256 j ascending,
+ *   the same tree), norm = sqrt(total), c = min(1, max_norm / (norm + 1e-6)) in fp64 (NaN stays NaN; max_norm <= 0: c = 1),
+ *   then per element with the host's scalars rounded to fp32:
+ *     g = c grad (+ weight_decay p: both products and the sum in fp64, rounded once);  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g g;
+ *     p -= step_size * (m / (sqrt(v) / bias2_sqrt + eps)),   step_size = lr / (1 - beta1^t), bias2_sqrt = sqrt(1 - beta2^t)
+ *   and *norm_out = norm (device double; may be NULL).  partial may cover more than this table (one norm over several
+ *   tables); npartial = 0 gives norm 0.  One launch.
+ * EAB_EINVAL before any launch: NULL table / pointers (a segment with n = 0 may hold NULL), n < 0, nseg outside
+ * [1, EAB_OPTIM_MAX_SEGMENTS], more than 2^24 chunks, a partial buffer that is too small.
+ * ------------------------------------------------------------------------ */
+#define EAB_OPTIM_MAX_SEGMENTS 8
+#define EAB_OPTIM_CHUNK 4096
+typedef struct {
+    float* param;             /* eab_adam_clip_f32 only */
+    const float* grad;
+    float* exp_avg;           /* eab_adam_clip_f32 only */
+    float* exp_avg_sq;        /* eab_adam_clip_f32 only */
+    long long n;
+} eab_optim_segment;
+int eab_grad_sumsq_f64(const eab_optim_segment* segs, int nseg, double* partial, long long partial_cap, eab_stream_t stream);
+int eab_adam_clip_f32(const eab_optim_segment* segs, int nseg, const double* partial, long long npartial, double max_norm,
+                      double step_size, double beta1, double beta2, double bias2_sqrt, double eps, double weight_decay,
+                      double* norm_out, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * K13  complex filter-and-sum, stand-alone.   Replaces EaBNet.py:114-117.
  *   w, x [B][T][F][M][2] -> y [B][2][T][F];  Y = sum_m W_m * X_m (no conjugate)
  * ------------------------------------------------------------------------ */
