@@ -144,6 +144,117 @@ static int istft_launch(const float* spec, const float* window, const float* twi
     EAB_RETURN_LAUNCH_STATUS();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Adjoint (eab_istft_bwd_f32): dwav [B][hop (T-1)] -> dspec [B][2][T][F].  The forward is linear in the spectrum, and a frame's
+// bins enter the wave only through that frame's own samples, so the frames do not interact: with p = t hop + idx, j = p - n_fft/2,
+//   u_t[idx] = w[idx] dwav[j] / env(p)  for 0 <= j < hop (Tb - 1), else 0          (env: the forward's envelope, in its order)
+//   dspec[.][t][k] = c_k / n_fft * rfft(u_t)[k],   c_k = 1 at k = 0 and n_fft/2, else 2;   Im = 0 at those two bins (C2R).
+// One workgroup owns FFT_SIGS consecutive frames of one utterance (no frame is shared between workgroups): it builds the u_t in LDS
+// (consecutive lanes -> consecutive samples of dwav; the float index of sample idx IS the packed z[idx/2].(re|im)), runs the
+// half-length transform once and splits it into the F bins as stft.hip does, one lane per pair (k, n_fft/2 - k), consecutive lanes
+// -> consecutive k of one frame: LDS reads and the stores of both rows are unit-stride (the mirrored bins descending).
+// Every output element is stored once, no atomics: the bits do not depend on scheduling.  Frames t >= Tb: zeros; dwav is never read
+// at j >= hop (Tb - 1).  Bound: HBM and launch latency (reads hop*4 B, writes 2*F*4 B per frame).
+template <bool VARLEN>
+__global__ __launch_bounds__(ISTFT_THREADS) void istft_bwd_kernel(const float* __restrict__ dwav, const float* __restrict__ window,
+                                                                  const float* __restrict__ twiddle, float* __restrict__ dspec,
+                                                                  int T, int n_fft, int hop, int chunks, FftPlan plan,
+                                                                  const int* __restrict__ lens) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int NH = n_fft / 2, F = NH + 1;
+    const int R = (n_fft + hop - 1) / hop;
+    float2* tw = reinterpret_cast<float2*>(smem);                 // [n_fft] exp(-2 pi i j / n_fft)
+    float2* buf0 = tw + n_fft;                                    // [FFT_SIGS][NH]
+    float2* buf1 = buf0 + FFT_SIGS * NH;
+    float* win = reinterpret_cast<float*>(buf1 + FFT_SIGS * NH);  // [n_fft]
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / chunks, chunk = blockIdx.x - b * chunks;
+    const int t0 = chunk * FFT_SIGS;
+    const int nfr = T - t0 < FFT_SIGS ? T - t0 : FFT_SIGS;        // frames of this workgroup that exist in dspec
+    const int Tb = VARLEN ? (lens[b] > T ? T : (lens[b] < 1 ? 1 : lens[b])) : T;
+    float* d0 = dspec + ((size_t)b * 2 * T + t0) * F;             // real rows of frames t0 .., contiguous; imaginary rows T*F on
+    float* d1 = d0 + (size_t)T * F;
+    if (VARLEN && t0 >= Tb) {                                     // (workgroup-uniform, before any barrier) all frames past the utterance
+        for (int e = tid; e < nfr * F; e += ISTFT_THREADS) d0[e] = d1[e] = 0.0f;
+        return;
+    }
+    for (int k = tid; k < n_fft; k += ISTFT_THREADS) {
+        const float2 cs = reinterpret_cast<const float2*>(twiddle)[k];
+        tw[k] = make_float2(cs.x, -cs.y);
+        win[k] = window[k];
+    }
+    __syncthreads();
+    const int out_len = hop * (T - 1), len_b = hop * (Tb - 1);
+    float* u = reinterpret_cast<float*>(buf0);
+    for (int e = tid; e < FFT_SIGS * n_fft; e += ISTFT_THREADS) {
+        const int c = e / n_fft, idx = e - c * n_fft;
+        const int t = t0 + c;
+        const int p = t * hop + idx, j = p - NH;
+        float v = 0.0f;
+        if (t < Tb && j >= 0 && j < len_b) {
+            const int th = p / hop;
+            float env = 0.0f;
+            for (int r = 0; r < R; ++r) {                         // the forward's envelope: highest frame first
+                const int tt = th - r;
+                const int ii = p - tt * hop;
+                if (tt < 0 || ii >= n_fft) break;
+                if (tt >= Tb) continue;
+                env = fmaf(win[ii], win[ii], env);
+            }
+            v = win[idx] * dwav[(size_t)b * out_len + j] / env;
+        }
+        u[e] = v;
+    }
+    __syncthreads();
+    const float2* z = fft_run(buf0, buf1, tw, NH, n_fft, plan, tid, ISTFT_THREADS);
+    // X[k] = E[k] + W^k O[k] and X[NH-k] = conj(E[k] - W^k O[k]) from the same two values (stft.hip)
+    const int NP = NH / 2 + 1;
+    const float inv = 1.0f / (float)n_fft;
+    for (int e = tid; e < nfr * NP; e += ISTFT_THREADS) {
+        const int c = e / NP, k = e - c * NP;
+        float* o0 = d0 + (size_t)c * F;
+        float* o1 = d1 + (size_t)c * F;
+        const bool twice = 2 * k != NH;
+        if (VARLEN && t0 + c >= Tb) {
+            o0[k] = o1[k] = 0.0f;
+            if (twice) o0[NH - k] = o1[NH - k] = 0.0f;
+            continue;
+        }
+        const float2 a = z[c * NH + k];
+        const float2 ac = z[c * NH + (k == 0 ? 0 : NH - k)];
+        const float2 E = make_float2(0.5f * (a.x + ac.x), 0.5f * (a.y - ac.y));
+        const float2 O = make_float2(0.5f * (a.y + ac.y), 0.5f * (ac.x - a.x));
+        const float2 wo = cmul(tw[k], O);
+        const float sc = k == 0 ? inv : 2.0f * inv;               // c_k / n_fft; k = 0 pairs DC with Nyquist
+        o0[k] = (E.x + wo.x) * sc;
+        o1[k] = k == 0 ? 0.0f : (E.y + wo.y) * sc;
+        if (twice) {
+            o0[NH - k] = (E.x - wo.x) * sc;
+            o1[NH - k] = k == 0 ? 0.0f : (wo.y - E.y) * sc;
+        }
+    }
+}
+
+extern "C" int eab_istft_bwd_f32(const float* dwav, const float* window, const float* twiddle, float* dspec, const int32_t* lens,
+                                 int B, int T, int n_fft, int hop, eab_stream_t stream) {
+    EAB_CHECK_ARG(dwav && window && twiddle && dspec);
+    EAB_CHECK_ARG(B > 0 && T >= 2 && hop > 0);
+    EAB_CHECK_ARG(n_fft >= 4 && n_fft <= ISTFT_MAX_NFFT && (n_fft % 2) == 0);
+    if (hop > n_fft || (n_fft + hop - 1) / hop > FFT_SIGS) return EAB_EUNSUPPORTED;
+    FftPlan plan;
+    if (!fft_plan(n_fft / 2, &plan)) return EAB_EUNSUPPORTED;
+    const int chunks = (T + FFT_SIGS - 1) / FFT_SIGS;
+    EAB_CHECK_ARG((long long)B * chunks < (1ll << 31) && (long long)hop * (T + FFT_SIGS) + n_fft < (1ll << 31));   // 32-bit positions
+    const size_t sh = (size_t)(2 * n_fft + 2 * FFT_SIGS * n_fft + n_fft) * sizeof(float);
+    if (lens)
+        hipLaunchKernelGGL(istft_bwd_kernel<true>, dim3(B * chunks), dim3(ISTFT_THREADS), sh, eab_stream(stream), dwav, window, twiddle,
+                           dspec, T, n_fft, hop, chunks, plan, lens);
+    else
+        hipLaunchKernelGGL(istft_bwd_kernel<false>, dim3(B * chunks), dim3(ISTFT_THREADS), sh, eab_stream(stream), dwav, window, twiddle,
+                           dspec, T, n_fft, hop, chunks, plan, lens);
+    EAB_RETURN_LAUNCH_STATUS();
+}
+
 extern "C" int eab_istft_f32(const float* spec, const float* window, const float* twiddle, float* wav, int B, int T,
                              int n_fft, int hop, eab_stream_t stream) {
     return istft_launch(spec, window, twiddle, wav, nullptr, B, T, n_fft, hop, stream);

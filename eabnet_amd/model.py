@@ -1271,20 +1271,33 @@ def prepare_data(x: torch.Tensor, target: torch.Tensor, device, args):
     return noisy_stft, target_stft
 
 
-_NOLA: Dict[tuple, bool] = {}
+_NOLA: Dict[tuple, object] = {}            # verdict; for a device window (verdict, the keyed tensor)
 
 
-def _check_nola(window: torch.Tensor, fft_num: int, hop: int, T: int) -> None:
+def _check_nola(window: torch.Tensor, fft_num: int, hop: int, T: int, key_window: Optional[torch.Tensor] = None) -> None:
     """torch.istft's window-overlap condition, on the host, before the kernel divides by the envelope: the squared-window
     overlap-add over the frames that exist must stay above 1e-11 at every output sample (a short zero-padded window with a
     large hop leaves gaps).  The envelope's two rims and its interior (periodic in the hop, whether or not the hop divides
-    fft_num) are those of a signal of 2R+2 frames, R = ceil(fft_num / hop)."""
-    w = window.detach().to("cpu", torch.float64).numpy()                     # (already zero-padded to fft_num by the caller)
-    key = (w.tobytes(), fft_num, hop, min(T, 2 * -(-fft_num // hop) + 2))   # by content: a pointer can be reused by another window
-    ok = _NOLA.get(key)
+    fft_num) are those of a signal of 2R+2 frames, R = ceil(fft_num / hop).  key_window: the caller's tensor that ``window`` was
+    padded from (a device window's verdict is cached under the tensor the caller holds, not under the padded temporary)."""
+    frames = min(T, 2 * -(-fft_num // hop) + 2)
+    src = window if key_window is None else key_window
+    if src.is_cuda:
+        # a device window is keyed by its storage and version counter and copied to the host on a miss only (inside a training
+        # step the copy would be a device synchronisation per step).  The entry keeps the keyed tensor alive, so its address
+        # cannot pass to another window while the verdict is cached; an in-place write bumps _version.
+        key = (str(src.device), src.data_ptr(), src._version, src.numel(), tuple(src.stride()), fft_num, hop, frames)
+        hit = _NOLA.get(key)
+        ok = None if hit is None else hit[0]
+    else:
+        w = window.detach().to(torch.float64).numpy()                        # (already zero-padded to fft_num by the caller)
+        key = (w.tobytes(), fft_num, hop, frames)                            # by content: a pointer can be reused by another window
+        ok = _NOLA.get(key)
     if ok is None:
+        if src.is_cuda:
+            w = window.detach().to("cpu", torch.float64).numpy()
         w2 = w ** 2
-        Te = key[-1]
+        Te = frames
         env = np.zeros(fft_num + hop * (Te - 1))
         for t in range(Te):
             env[t * hop:t * hop + fft_num] += w2
@@ -1292,10 +1305,48 @@ def _check_nola(window: torch.Tensor, fft_num: int, hop: int, T: int) -> None:
         ok = bool(trimmed.size == 0 or np.abs(trimmed).min() > 1e-11)
         if len(_NOLA) > 64:
             _NOLA.clear()
-        _NOLA[key] = ok
+        _NOLA[key] = (ok, src) if src.is_cuda else ok
     if not ok:
         raise RuntimeError("istft: window overlap add min is below 1e-11 (the NOLA condition of torch.istft fails for this "
                            f"window / hop: fft_num={fft_num}, win_shift={hop})")
+
+
+class _Istft(torch.autograd.Function):
+    """``istft`` on an input that requires grad: the forward is the launch ``istft`` makes for any other input (the same
+    values), the backward the adjoint kernel eab_istft_bwd_f32 on the same window and, where given, the same lengths."""
+
+    @staticmethod
+    def forward(ctx, esti: torch.Tensor, window: torch.Tensor, lengths, fft_num: int, hop: int) -> torch.Tensor:
+        lib = _lib.load()
+        B, _, T, _ = esti.shape
+        x = esti.detach().to(torch.float32).contiguous()
+        wav = torch.empty((B, hop * (T - 1)), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            tw = _twiddle(fft_num, x.device)
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            lens = None if lengths is None else _device_lengths(lengths, x.device)
+            if lens is not None:
+                _lib.check(lib.eab_istft_lens_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(), lens.data_ptr(),
+                                                  B, T, fft_num, hop, stream), "eab_istft_lens_f32")
+            else:
+                _lib.check(lib.eab_istft_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(), B, T, fft_num, hop,
+                                             stream), "eab_istft_f32")
+        ctx.save_for_backward(window, tw, *(() if lens is None else (lens,)))
+        ctx.geom = (B, T, fft_num, hop, esti.dtype)
+        return wav
+
+    @staticmethod
+    def backward(ctx, dwav):
+        window, tw, *rest = ctx.saved_tensors
+        B, T, fft_num, hop, dtype = ctx.geom
+        lib = _lib.load()
+        g = dwav.detach().to(torch.float32).contiguous()
+        dspec = torch.empty((B, 2, T, fft_num // 2 + 1), dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(lib.eab_istft_bwd_f32(g.data_ptr(), window.data_ptr(), tw.data_ptr(), dspec.data_ptr(),
+                                             rest[0].data_ptr() if rest else None, B, T, fft_num, hop,
+                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_istft_bwd_f32")
+        return dspec.to(dtype), None, None, None, None
 
 
 def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.Tensor, lengths=None) -> torch.Tensor:
@@ -1307,7 +1358,11 @@ def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.T
     lengths: optional (B,) frame counts, 2 <= len <= T (a sequence or an integer tensor, host or device): utterance b is
     esti_stft[b, :, :len[b]], later frames are never read.  Its first win_shift*(len[b]-1) samples are those of a call on
     that utterance alone, bit for bit (the envelope counts its own frames only); the samples after them are zeros.  The
-    window-overlap condition is checked for the shortest and the longest host length (a device tensor: for T)."""
+    window-overlap condition is checked for the shortest and the longest host length (a device tensor: for T).
+
+    Differentiable: with grad enabled and ``esti_stft.requires_grad`` the same launch runs inside an autograd node whose
+    backward is the adjoint kernel (eab_istft_bwd_f32), so a loss on the wave -- ``si_sdr_loss`` -- trains
+    the network.  The values are those of the call without grad, bit for bit; the gradient has the input's dtype."""
     if lengths is not None:
         if esti_stft.ndim != 4:
             raise ValueError(f"expected (B,2,T,{fft_num // 2 + 1}), got {tuple(esti_stft.shape)}")
@@ -1320,6 +1375,7 @@ def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.T
         raise RuntimeError(f"window ({window.numel()} samples) must not exceed fft_num ({fft_num}), as in torch.istft")
     if not 0 < win_shift <= window.numel():
         raise RuntimeError(f"istft: expected 0 < win_shift <= win_length, got {win_shift} and {window.numel()} (as torch.istft)")
+    given = window
     if window.numel() < fft_num:                  # torch.istft(win_length < n_fft): zero-padded on both sides, centred
         left = (fft_num - window.numel()) // 2
         window = torch.nn.functional.pad(window, (left, fft_num - window.numel() - left))
@@ -1329,7 +1385,10 @@ def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.T
     lib = _lib.load()
     B, _, T, _ = esti_stft.shape
     for n in ((T,) if lengths is None or isinstance(lengths, torch.Tensor) else sorted({min(lengths), max(lengths)})):
-        _check_nola(window, fft_num, win_shift, n)
+        _check_nola(window, fft_num, win_shift, n, key_window=given)
+    if torch.is_grad_enabled() and esti_stft.requires_grad:
+        # training on the waveform: the same launch, with eab_istft_bwd_f32 as its backward
+        return _Istft.apply(esti_stft, _device_window(window, esti_stft.device), lengths, fft_num, win_shift)
     x = esti_stft.detach().to(torch.float32).contiguous()
     window = _device_window(window, x.device)
     wav = torch.empty((B, win_shift * (T - 1)), dtype=torch.float32, device=x.device)

@@ -128,6 +128,20 @@ int eab_istft_f32(const float* spec, const float* window, const float* twiddle, 
 int eab_istft_lens_f32(const float* spec, const float* window, const float* twiddle, float* wav, const int32_t* lens,
                        int B, int T_cap, int n_fft, int hop, eab_stream_t stream);
 
+/* The adjoint of the back end (training on the waveform): the gradient of a scalar with respect to `spec`, given its gradient
+ * `dwav` with respect to the wave of eab_istft_f32 (lens == NULL) or eab_istft_lens_f32 (lens: the same DEVICE frame counts).
+ *   dwav    [B][hop*(T-1)]
+ *   dspec   [B][2][T][F]
+ * With NH = n_fft/2, Tb = lens[b] clamped to [1, T] (T without lens), env(p) the squared-window envelope of the frames
+ * t' < Tb that cover the padded position p, p = t hop + idx and j = p - NH:
+ *   u_t[idx] = window[idx] * dwav[b][j] / env(p)   for 0 <= j < hop (Tb - 1), else 0
+ *   dspec[b][0|1][t][k] = c_k / n_fft * (Re|Im) rfft(u_t)[k],   c_k = 1 for k = 0 and k = NH, else 2
+ * The imaginary parts at k = 0 and k = NH are exactly 0 (the C2R transform ignores them).  Frames t >= Tb are written as exact
+ * zeros and dwav is never read at j >= hop (Tb - 1).  Every element is stored once, no atomics: the same bits in every call.
+ * Limits and return codes as eab_istft_f32.  Only an entry point is added: EAB_ABI_VERSION stays 10. */
+int eab_istft_bwd_f32(const float* dwav, const float* window, const float* twiddle, float* dspec, const int32_t* lens,
+                      int B, int T, int n_fft, int hop, eab_stream_t stream);
+
 /* --------------------------------------------------------------------------
  * GaGNet post-filter glue (reference GaGNet.py).  The convolutions of the post-filter
  * run on eab_conv_f32; these are the two elementwise passes around them.
@@ -195,6 +209,38 @@ int eab_energy_ratios_f32(const float* est, long long est_stride, int est_cap, c
                           double* partial, int partial_spans, double* out, eab_stream_t stream);
 int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* label, const int32_t* frames, int B, int T_esti, int T_label,
                                   int F, double* partial, int partial_spans, double* loss, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
+ * Waveform training loss: negative SI-SDR per utterance of a padded batch, value and gradient (csrc/wave_loss.hip) -- the
+ * si_sdr of eab_energy_ratios_f32 (metrics.py:71-75) as a loss.  Only entry points are added: EAB_ABI_VERSION stays 10.
+ *
+ *   est, clean: row b of a signal starts at base + b*stride (floats) and is read in place; at most `cap` floats of it
+ *   lens    DEVICE int32 [B][2]: samples of (est, clean) of utterance b, clamped to [0, cap]; a signal counts as zero from
+ *           its own length up to the longer of the two, and is never read there
+ * With k = 10 / ln 10, es = <e,s>, ss = <s,s>, ee = <e,e>, alpha = es/ss, tgt = es^2/ss, res = ee - tgt:
+ *   loss_b = -k [ ln(tgt + eps) - ln(res + eps) ]                      (eps = 0: minus the si_sdr of eab_energy_ratios_f32)
+ *   d loss_b / d e_i = a_b e_i + c_b s_i   for i < lens[b][0],   a_b = 2k / (res + eps),
+ *                                                                c_b = -2k alpha [1 / (tgt + eps) + 1 / (res + eps)]
+ * eab_si_sdr_loss_f32 (two launches):
+ *   eps     >= 0, finite
+ *   partial device scratch of B * partial_spans * 3 doubles, partial_spans >= ceil(max(cap) / 4096)
+ *   out     device double [B][3]: loss_b, a_b, c_b.  A silent clean row gives NaN in ITS row.
+ *   loss    device float [B]: loss_b;   total  device float [2]: the sum and the mean of loss_b over the batch
+ * eab_si_sdr_loss_bwd_f32 (one launch): grad[b][i] = grad_out[b * grad_out_stride] * scale * (a_b e_i + c_b s_i) for
+ * i < lens[b][0] and exactly 0 from there to est_cap.
+ *   coef    the `out` of the forward call on the same rows and lens
+ *   grad_out DEVICE float, one weight per utterance grad_out_stride >= 0 floats apart (0: one weight for all) -- the
+ *           grad_output of autograd, read on the device
+ *   grad    float rows of est_cap floats, grad_stride floats apart (16-byte stores where the address allows)
+ * Sums and products in fp64 over fixed spans of 4096 samples added in index order, no atomics: an utterance has the same bits
+ * alone and in any batch, whatever the strides and alignments.
+ * ------------------------------------------------------------------------ */
+int eab_si_sdr_loss_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
+                        int clean_cap, const int32_t* lens, int B, double eps, double* partial, int partial_spans, double* out,
+                        float* loss, float* total, eab_stream_t stream);
+int eab_si_sdr_loss_bwd_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
+                            int clean_cap, const int32_t* lens, int B, const double* coef, const float* grad_out,
+                            int grad_out_stride, double scale, float* grad, long long grad_stride, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
  * Intelligibility per utterance of a padded batch at 10 kHz (csrc/stoi.hip): STOI and ESTOI of cal_single_metrics
