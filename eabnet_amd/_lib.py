@@ -99,6 +99,12 @@ _SIGS = {
                             + [C.c_void_p] * 4),
     "eab_si_sdr_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_double, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "eab_mrstft_workspace_bytes": (C.c_longlong, [C.c_void_p] + [C.c_int] * 4),
+    "eab_mrstft_loss_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+                            + [C.c_double] * 3 + [C.c_void_p, C.c_longlong] + [C.c_void_p] * 4),
+    "eab_mrstft_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_longlong,
+                                          C.c_void_p, C.c_longlong, C.c_void_p]),
     "eab_norm_act_win_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 4 + [TimeWindow, C.c_void_p]),
     "eab_lstm64_stream_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 4 + [C.c_int] * 4
                               + [TimeWindow, C.c_void_p]),

@@ -6,10 +6,14 @@
     loss = l["final"] + w * si_sdr_loss(wav, target, eps=1e-8)
     loss.backward()
 
-Two launches for the value, one for the gradient; ``grad_output`` is read on the device, nothing synchronises with the host."""
+Two launches for the value, one for the gradient; ``grad_output`` is read on the device, nothing synchronises with the host.
+
+``mr_stft_loss`` is the spectral half of a waveform objective -- spectral convergence plus log-magnitude distance at several
+time-frequency resolutions, csrc/spec_loss.hip -- added the same way: ``loss = loss + v * mr_stft_loss(wav, target)``."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -125,3 +129,169 @@ def si_sdr_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, eps: float
     with torch.cuda.device(est.device):
         lens = _lens(cols, B, est.device)
     return _SiSdrLoss.apply(est_rows, clean_rows, lens, float(eps), reduction)
+
+
+MR_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))
+MR_MAX_RESOLUTIONS = 8
+MR_MAX_NFFT = 2048
+MR_MAX_COVER = 8        # frames whose window support covers one sample: ceil(win / hop)
+FFT_MAX_PASSES = 8
+_MR_TABLES: dict = {}
+
+
+def _fft_passes(n: int):
+    """the passes csrc/fft_lds.h plans for an n-point transform (radix 5s, 4s, a trailing 8, 2s), or None where n has another
+    prime factor or the plan runs out of passes"""
+    passes = 0
+    while n % 5 == 0 and passes < FFT_MAX_PASSES:
+        n, passes = n // 5, passes + 1
+    while n % 4 == 0 and n != 8 and passes < FFT_MAX_PASSES:
+        n, passes = n // 4, passes + 1
+    if n == 8:
+        n, passes = 1, passes + 1
+    while n % 2 == 0 and passes < FFT_MAX_PASSES:
+        n, passes = n // 2, passes + 1
+    return passes if n == 1 else None
+
+
+def check_resolutions(resolutions) -> tuple:
+    """``resolutions`` as a tuple of (n_fft, hop, win) integer triples the LDS transform can plan, or ValueError with the reason"""
+    try:
+        res = [tuple(r) for r in resolutions]
+    except TypeError:
+        raise ValueError(f"resolutions must be a sequence of (n_fft, hop, win) triples, got {resolutions!r}") from None
+    if not 1 <= len(res) <= MR_MAX_RESOLUTIONS:
+        raise ValueError(f"resolutions must hold 1 to {MR_MAX_RESOLUTIONS} (n_fft, hop, win) triples, got {len(res)}")
+    for r in res:
+        if len(r) != 3 or any(isinstance(v, bool) or not isinstance(v, int) for v in r):
+            raise ValueError(f"a resolution is a triple of integers (n_fft, hop, win), got {r!r}")
+        n_fft, hop, win = r
+        if n_fft % 2 or not 8 <= n_fft <= MR_MAX_NFFT:
+            raise ValueError(f"resolution {r}: n_fft must be even and lie in [8, {MR_MAX_NFFT}] (the transform runs in LDS)")
+        if _fft_passes(n_fft // 2) is None:
+            raise ValueError(f"resolution {r}: n_fft / 2 = {n_fft // 2} must be 2^a 5^b within {FFT_MAX_PASSES} passes "
+                             "(the radices of the LDS transform)")
+        if not 1 <= hop <= n_fft or not 1 <= win <= n_fft:
+            raise ValueError(f"resolution {r}: hop and win must lie in [1, n_fft]")
+        if -(-win // hop) > MR_MAX_COVER:
+            raise ValueError(f"resolution {r}: at most {MR_MAX_COVER} windows may cover one sample (ceil(win / hop) = {-(-win // hop)})")
+    return tuple(res)
+
+
+def _mr_tables(res: tuple, device: torch.device) -> torch.Tensor:
+    """per resolution the zero-padded periodic Hann window (n_fft,) and (cos, sin)(2 pi j / n_fft) (n_fft, 2), fp32 from float64"""
+    key = (res, str(device))
+    if key not in _MR_TABLES:
+        parts = []
+        for n_fft, _, win in res:
+            w = torch.zeros(n_fft, dtype=torch.float64)
+            left = (n_fft - win) // 2
+            w[left:left + win] = torch.hann_window(win, dtype=torch.float64)
+            th = 2.0 * math.pi * torch.arange(n_fft, dtype=torch.float64) / n_fft
+            parts += [w, torch.stack([torch.cos(th), torch.sin(th)], dim=1).reshape(-1)]
+        _MR_TABLES[key] = torch.cat(parts).to(torch.float32).to(device)
+    return _MR_TABLES[key]
+
+
+class _MrStftLoss(torch.autograd.Function):
+    """value: eab_mrstft_loss_f32 leaves loss_b and two coefficients per (utterance, resolution); backward:
+    eab_mrstft_loss_bwd_f32 recomputes the spectra and gathers the frames' gradients, scaled by grad_output on the device"""
+
+    @staticmethod
+    def forward(ctx, est, clean, lens, res, factor_sc, factor_mag, floor, reduction):
+        lib = _lib.load()
+        B, R = est.shape[0], len(res)
+        e, s = est.detach(), clean
+        cap = min(e.shape[1], s.shape[1])
+        res_host = (C.c_int32 * (3 * R))(*[v for r in res for v in r])
+        with torch.cuda.device(e.device):
+            tables = _mr_tables(res, e.device)
+            nbytes = lib.eab_mrstft_workspace_bytes(res_host, R, B, cap, 0)
+            if nbytes < 0:
+                raise _lib.EabError("eab_mrstft_workspace_bytes refused the resolutions or the rows")
+            work = torch.empty((nbytes // 8,), dtype=torch.float64, device=e.device)
+            coef = torch.empty((B, R, 2), dtype=torch.float64, device=e.device)
+            loss = torch.empty((B,), dtype=torch.float32, device=e.device)
+            total = torch.empty((2,), dtype=torch.float32, device=e.device)
+            _lib.check(lib.eab_mrstft_loss_f32(*_row_args(B, e, s), lens.data_ptr(), B, res_host, R, tables.data_ptr(), factor_sc,
+                                               factor_mag, floor, work.data_ptr(), nbytes, coef.data_ptr(), loss.data_ptr(),
+                                               total.data_ptr(), _stream()), "eab_mrstft_loss_f32")
+        ctx.save_for_backward(e, s, lens, coef, tables)
+        ctx.res, ctx.floor, ctx.reduction = res, floor, reduction
+        return loss if reduction == "none" else total[0 if reduction == "sum" else 1]
+
+    @staticmethod
+    def backward(ctx, g):
+        e, s, lens, coef, tables = ctx.saved_tensors
+        lib = _lib.load()
+        B, L = e.shape
+        res, R = ctx.res, len(ctx.res)
+        res_host = (C.c_int32 * (3 * R))(*[v for r in res for v in r])
+        g = g.detach()
+        if g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        per_row = ctx.reduction == "none"
+        gstride = g.stride(0) if per_row and B > 1 else 0
+        if gstride < 0:
+            g, gstride = g.contiguous(), 1
+        with torch.cuda.device(e.device):
+            nbytes = lib.eab_mrstft_workspace_bytes(res_host, R, B, min(L, s.shape[1]), 1)
+            work = torch.empty((nbytes // 4,), dtype=torch.float32, device=e.device)
+            grad = torch.empty((B, L), dtype=torch.float32, device=e.device)
+            _lib.check(lib.eab_mrstft_loss_bwd_f32(*_row_args(B, e, s), lens.data_ptr(), B, res_host, R, tables.data_ptr(), ctx.floor,
+                                                   coef.data_ptr(), g.data_ptr(), gstride, 1.0 / B if ctx.reduction == "mean" else 1.0,
+                                                   work.data_ptr(), nbytes, grad.data_ptr(), L, _stream()), "eab_mrstft_loss_bwd_f32")
+        return grad, None, None, None, None, None, None, None
+
+
+def mr_stft_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, resolutions=MR_RESOLUTIONS, factor_sc: float = 1.0,
+                 factor_mag: float = 1.0, floor: float = 1e-7, reduction: str = "mean") -> torch.Tensor:
+    """Multi-resolution STFT loss of B utterances, differentiable with respect to ``est``: est (B, Le), clean (B, Ls) or (B, 1, Ls),
+    CUDA fp32 -> an fp32 scalar (``reduction`` "mean" or "sum") or (B,) ("none").  For every resolution (n_fft, hop, win), with X =
+    torch.stft(x[:n_b], n_fft, hop, win, hann_window(win), center=True, pad_mode="reflect"), P = max(|X|^2, floor), E = sqrt(P_est),
+    S = sqrt(P_clean) over the utterance's own T = 1 + n_b // hop frames and F = n_fft/2 + 1 bins:
+
+        loss_b = 1/R sum_r [ factor_sc sqrt(sum (S - E)^2) / sqrt(sum S^2) + factor_mag / (T F) sum |ln S - ln E| ]
+
+    The norms are per utterance (the published implementations take them over the batch; at B = 1 the two agree), so an utterance
+    has the same bits alone, in any batch and in a second call, value and gradient.  The gradient is zero through a clamped bin and
+    where sum (S - E)^2 = 0 its spectral-convergence part is taken as zero.  lengths: None (n_b = min(Le, Ls)) or (B,) sample counts
+    <= min(Le, Ls), a sequence or integer tensor, host or device; n_b > max n_fft / 2 (reflect padding).  Samples at and past n_b
+    are never read and the gradient is exactly zero from n_b to Le.  Rows may be strided views whose last dimension is contiguous
+    and are read in place.  A resolution must have n_fft even in [8, 2048] with n_fft / 2 = 2^a 5^b, hop and win in [1, n_fft] and
+    ceil(win / hop) <= 8; at most 8 resolutions.  No operator fallback: CPU tensors, other dtypes and a ``clean`` that requires grad
+    raise."""
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    if not (isinstance(floor, (int, float)) and 0.0 < float(floor) < float("inf")):
+        raise ValueError(f"floor must be a finite number > 0, got {floor!r}")
+    for name, v in (("factor_sc", factor_sc), ("factor_mag", factor_mag)):
+        if not (isinstance(v, (int, float)) and 0.0 <= float(v) < float("inf")):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    res = check_resolutions(resolutions)
+    if clean.ndim == 3 and clean.shape[1] == 1:
+        clean = clean[:, 0]
+    for name, t in (("est", est), ("clean", clean)):
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be a (B, L) tensor (clean may be (B, 1, L)), got {tuple(t.shape)}")
+    B = est.shape[0]
+    if clean.shape[0] != B:
+        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
+    if est.dtype != torch.float32 or clean.dtype != torch.float32:
+        raise TypeError(f"mr_stft_loss takes fp32 waves, got {est.dtype} and {clean.dtype} (there is no operator fallback)")
+    if clean.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("mr_stft_loss is differentiable with respect to est only: clean requires grad (detach it; "
+                                  "there is no operator fallback)")
+    cap, nmin = min(est.shape[1], clean.shape[1]), max(r[0] for r in res) // 2 + 1
+    if cap < nmin:
+        raise ValueError(f"rows of {cap} samples are too short for reflect padding: more than {nmin - 1} (max n_fft / 2) are needed")
+    lens = [cap] * B if lengths is None else _m.check_lengths(lengths, B, cap, lo=nmin, unit="max n_fft / 2 < samples <= min(Le, Ls)",
+                                                              integral=True)
+    if not (est.is_cuda and clean.is_cuda):
+        raise _lib.EabError("mr_stft_loss needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+    if est.device != clean.device:
+        raise ValueError("est and clean must be on one device")
+    est_rows, clean_rows = _rows_in_place(est), _rows_in_place(clean.detach())
+    with torch.cuda.device(est.device):
+        lens = _m._device_lengths(lens, est.device)
+    return _MrStftLoss.apply(est_rows, clean_rows, lens, res, float(factor_sc), float(factor_mag), float(floor), reduction)

@@ -243,6 +243,48 @@ int eab_si_sdr_loss_bwd_f32(const float* est, long long est_stride, int est_cap,
                             int grad_out_stride, double scale, float* grad, long long grad_stride, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * Multi-resolution STFT loss on the waveform, value and gradient (csrc/spec_loss.hip; definition and deviations: DESIGN.md §4.21).
+ * Only entry points are added: EAB_ABI_VERSION stays 10.
+ *
+ *   est, clean: rows as for the SI-SDR loss above, read in place; cap = min(est_cap, clean_cap)
+ *   lens    DEVICE int32 [B]: samples n_b of utterance b (both signals), clamped to [max n_fft / 2 + 1, cap]; neither signal is
+ *           read at or past n_b
+ *   res     HOST int32 [R][3]: (n_fft, hop, win) per resolution, 1 <= R <= 8.  Refused (EAB_EINVAL) unless n_fft is even,
+ *           8 <= n_fft <= 2048, n_fft / 2 = 2^a 5^b within the transform's passes, 1 <= hop <= n_fft, 1 <= win <= n_fft,
+ *           ceil(win / hop) <= 8 (frames whose window support covers one sample) and cap > max n_fft / 2 (reflect padding)
+ *   tables  DEVICE float: per resolution, in order, window[n_fft] (the periodic Hann window of `win` samples zero-padded from
+ *           offset (n_fft - win) / 2) followed by n_fft pairs (cos, sin)(2 pi j / n_fft): 3 * sum n_fft floats
+ * With P = max(re^2 + im^2, floor), E = sqrt(P_est), S = sqrt(P_clean) over the T = 1 + n_b / hop frames and F = n_fft/2 + 1
+ * bins of torch.stft(x[:n_b], n_fft, hop, win, hann, center=True, pad_mode="reflect"):
+ *   loss_b = 1/R sum_r [ factor_sc sqrt(sum (S - E)^2) / sqrt(sum S^2) + factor_mag / (T F) sum |ln S - ln E| ]
+ * eab_mrstft_workspace_bytes: bytes of `work` for the value (backward = 0) or the gradient (backward != 0); -1 for arguments the
+ *   calls refuse.
+ * eab_mrstft_loss_f32 (R + 1 launches):
+ *   factor_sc, factor_mag >= 0 and finite; floor > 0
+ *   work    device scratch, 8-byte aligned, eab_mrstft_workspace_bytes(res, R, B, cap, 0) bytes
+ *   coef    device double [B][R][2]: what the gradient needs per (utterance, resolution)
+ *   loss    device float [B]: loss_b;   total  device float [2]: the sum and the mean of loss_b over the batch
+ * eab_mrstft_loss_bwd_f32 (R + 1 launches): grad[b][i] = grad_out[b * grad_out_stride] * scale * d loss_b / d est[b][i] for
+ * i < n_b and exactly 0 from there to est_cap.  Zero through a clamped bin; the spectral-convergence part is zero where
+ * sum (S - E)^2 = 0.
+ *   coef    the `coef` of the value call on the same rows, lens, res and floor
+ *   grad_out DEVICE float, one weight per utterance grad_out_stride >= 0 floats apart (0: one weight for all)
+ *   work    device scratch, eab_mrstft_workspace_bytes(res, R, B, cap, 1) bytes
+ *   grad    float rows of est_cap floats, grad_stride floats apart
+ * fp64 sums in one fixed order, no atomics: an utterance has the same bits alone, in any batch, at any alignment and in a
+ * second call, value and gradient.
+ * ------------------------------------------------------------------------ */
+long long eab_mrstft_workspace_bytes(const int32_t* res, int R, int B, int cap, int backward);
+int eab_mrstft_loss_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
+                        int clean_cap, const int32_t* lens, int B, const int32_t* res, int R, const float* tables,
+                        double factor_sc, double factor_mag, double floor, void* work, long long work_bytes, double* coef,
+                        float* loss, float* total, eab_stream_t stream);
+int eab_mrstft_loss_bwd_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
+                            int clean_cap, const int32_t* lens, int B, const int32_t* res, int R, const float* tables,
+                            double floor, const double* coef, const float* grad_out, int grad_out_stride, double scale,
+                            void* work, long long work_bytes, float* grad, long long grad_stride, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * Intelligibility per utterance of a padded batch at 10 kHz (csrc/stoi.hip): STOI and ESTOI of cal_single_metrics
  * (test.py:126-153), by the definition of DESIGN.md §4.16 (the definition is the contract; equality with a host STOI library
  * is not verified).  Only entry points are added: EAB_ABI_VERSION stays 10.
