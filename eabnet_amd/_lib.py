@@ -121,6 +121,12 @@ _SIGS = {
     "eab_stoi_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "eab_stoi_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong]
                      + [C.c_void_p] * 5),
+    "eab_stoi_bwd_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
+    "eab_stoi_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong,
+                                   C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_longlong, C.c_void_p,
+                                   C.c_longlong, C.c_void_p]),
+    "eab_resample_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "eab_resample_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                    C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p]),

@@ -183,3 +183,69 @@ extern "C" int eab_resample_f32(const float* x, long long x_row_stride, int x_co
     }
     return four ? rs_launch<4, false, false>(a, rows, stream) : rs_launch<1, false, false>(a, rows, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The adjoint of the whole-signal resampler (both origins 0, no row map): input sample j of a row collects
+//     gx[j] = sum tab[p][k] * gy[q*n + p]       over the (q, p, k) with q*o + first[p] + k == j
+// as a gather, one thread per input sample, in ascending output index q*n + p and one fmaf per term: ONE order per sample, so its
+// bits do not depend on the batch.  For a quotient q the phases that reach j are those with j - q*o - K < first[p] <= j - q*o: one
+// run of p, because first[] is nondecreasing, found by two binary searches.  Outputs at and past ceil(n*len/o) carry no gradient
+// (the forward wrote zeros there) and gx is zero from len on.  The bank and gy are read through the caches: a sample takes about
+// K*n/o terms (12 at 16 -> 10 kHz).
+struct ResampleBwdArgs {
+    const float* gy; long long gy_row_stride; int n_out; const int32_t* in_lens; int rows_per_utt;
+    float* gx; long long gx_row_stride; int x_cols;
+    const float* tab; const int32_t* first; int o, n, K;
+};
+
+__device__ __forceinline__ int rs_floor_div(int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+// the first p in [0, n) with first[p] > v (n if none)
+__device__ __forceinline__ int rs_first_above(const int32_t* __restrict__ first, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] > v) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(RS_THREADS) void resample_bwd_kernel(const ResampleBwdArgs a) {
+    const int j = blockIdx.x * RS_THREADS + threadIdx.x, row = blockIdx.y;
+    if (j >= a.x_cols) return;
+    const int o = a.o, n = a.n, K = a.K;
+    int hi = a.x_cols, out_hi = a.n_out;
+    if (a.in_lens) {
+        hi = max(0, min(a.in_lens[row / a.rows_per_utt], a.x_cols));
+        out_hi = (int)min((long long)a.n_out, ((long long)hi * n + o - 1) / o);
+    }
+    float acc = 0.0f;
+    if (j < hi) {
+        const float* __restrict__ gyr = a.gy + (long long)row * a.gy_row_stride;
+        const int q_lo = max(0, rs_floor_div(j - a.first[n - 1] - K, o) + 1), q_hi = rs_floor_div(j - a.first[0], o);
+        for (int q = q_lo; q <= q_hi; ++q) {
+            const int r = j - q * o;                                    // first[p] + k == r with 0 <= k < K
+            const int p_end = rs_first_above(a.first, n, r);
+            for (int p = rs_first_above(a.first, n, r - K); p < p_end; ++p) {
+                const long long i = (long long)q * n + p;
+                if (i >= out_hi) break;
+                acc = fmaf(a.tab[p * K + (r - a.first[p])], gyr[i], acc);
+            }
+        }
+    }
+    a.gx[(long long)row * a.gx_row_stride + j] = acc;
+}
+
+extern "C" int eab_resample_bwd_f32(const float* gy, long long gy_row_stride, int n_out, const int32_t* in_lens, int rows,
+                                    int rows_per_utt, float* gx, long long gx_row_stride, int x_cols, const float* tab,
+                                    const int32_t* first, int o, int n, int K, eab_stream_t stream) {
+    EAB_CHECK_ARG(gy && gx && tab && first);
+    EAB_CHECK_ARG(o >= 1 && n >= 1 && K >= 1 && (long long)K * n <= RS_MAX_BANK);
+    EAB_CHECK_ARG(rows >= 0 && rows <= 65535 && rows_per_utt >= 1 && x_cols >= 0 && x_cols <= RS_MAX_COLS && n_out >= 0);
+    EAB_CHECK_ARG(rows <= 1 || (gy_row_stride >= n_out && gx_row_stride >= x_cols));
+    if (rows == 0 || x_cols == 0) return EAB_OK;
+    const ResampleBwdArgs a{gy, gy_row_stride, n_out, in_lens, rows_per_utt, gx, gx_row_stride, x_cols, tab, first, o, n, K};
+    hipLaunchKernelGGL(resample_bwd_kernel, dim3((unsigned)((x_cols + RS_THREADS - 1) / RS_THREADS), (unsigned)rows), dim3(RS_THREADS),
+                       0, eab_stream(stream), a);
+    EAB_RETURN_LAUNCH_STATUS();
+}

@@ -194,6 +194,36 @@ def _resample_rows(x3: torch.Tensor, orig_freq: int, new_freq: int, lens_in, ord
     return y
 
 
+class _Resample(torch.autograd.Function):
+    """the forward is ``_resample_rows``' one launch, unchanged; the backward is eab_resample_bwd_f32, the bank's adjoint as a
+    gather per input sample (ascending output index, one fmaf per term)"""
+
+    @staticmethod
+    def forward(ctx, x3: torch.Tensor, lens, n_out: int, args: tuple) -> torch.Tensor:
+        x3 = x3.detach()
+        if lens is not None:
+            with torch.cuda.device(x3.device):
+                lens = _m._device_lengths(lens, x3.device)
+        ctx.lens, ctx.args, ctx.shape = lens, args, tuple(x3.shape)
+        return _resample_rows(x3, args[0], args[1], lens, None, n_out, *args[2:])
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        B, M, L = ctx.shape
+        gy = gy.detach().to(torch.float32).contiguous()
+        n_out = gy.shape[-1]
+        with torch.cuda.device(gy.device):
+            tab, first, o, n, K = _device_bank(*ctx.args, gy.device)
+            gx = torch.empty((B, M, L), dtype=torch.float32, device=gy.device)
+            if B * M and L:
+                _lib.check(_lib.load().eab_resample_bwd_f32(
+                    gy.data_ptr(), n_out, n_out, None if ctx.lens is None else ctx.lens.data_ptr(), B * M, M, gx.data_ptr(), L, L,
+                    tab.data_ptr(), first.data_ptr(), o, n, K, C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                    "eab_resample_bwd_f32")
+        return gx, None, None, None
+
+
 def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lengths=None, mic_order=None, window: str = "hann",
              lowpass_filter_width: int = 6, rolloff: float = 0.99) -> torch.Tensor:
     """(..., L) CUDA fp32 at ``orig_freq`` -> (..., ceil(n L / o)) at ``new_freq`` (module docstring); ``orig_freq == new_freq``
@@ -204,7 +234,12 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lengths=None, mic
     those of a call on it alone, bit for bit, and the rest of its output rows is zero.  mic_order: a permutation, or a
     selection with repeats, of the second-to-last dimension, applied while reading (``wav[..., mic_order, :]`` at no cost).
     Rows are read in place when the last dimension is contiguous and the leading strides are multiples of one row pitch (a
-    channel block of a wider buffer); anything else is copied first."""
+    channel block of a wider buffer); anything else is copied first.
+
+    A ``wav`` that requires grad goes through an autograd node: the same launch and the same bits forward, the bank's adjoint
+    (one gather launch) backward -- zero past a row's length, and outputs past ceil(n len / o) carry no gradient.  ``mic_order``
+    is refused there (a selection with repeats would need a row sum); a ``wav`` that does not require grad takes the plain
+    path."""
     if wav.ndim < 1:
         raise ValueError("resample takes a (..., L) tensor")
     o, n = _ratio(orig_freq, new_freq)
@@ -214,6 +249,10 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lengths=None, mic
         if wav.ndim < 2:
             raise ValueError("mic_order needs a (..., M, L) tensor")
         order = check_mic_order(mic_order, wav.shape[-2])
+    diff = wav.requires_grad and torch.is_grad_enabled()
+    if diff and order is not None:
+        raise NotImplementedError("resample is differentiable without mic_order only (a selection with repeats would need a "
+                                  "row sum); index the waves first.  There is no operator fallback.")
     if lengths is not None:
         if wav.ndim not in (2, 3) or (wav.ndim == 2 and order is not None):
             raise ValueError(f"lengths needs a padded (B, M, L) batch, or (B, L) without mic_order, got {tuple(wav.shape)}")
@@ -245,7 +284,12 @@ def resample(wav: torch.Tensor, orig_freq: int, new_freq: int, lengths=None, mic
         x3 = wav.reshape((groups,) + tuple(wav.shape[-2:]))               # (a view where it can be, a copy where not)
     if lengths is not None and wav.ndim == 2:
         x3 = x3.transpose(0, 1)                                           # (B, L): every row an utterance of its own
-    y = _resample_rows(x3, orig_freq, new_freq, lengths, order, n_out, window, lowpass_filter_width, rolloff)
+    if diff:
+        if x3.shape[0] * x3.shape[1] > 65535:
+            raise ValueError(f"resample takes at most 65535 rows per call, got {x3.shape[0] * x3.shape[1]}")
+        y = _Resample.apply(x3, lengths, n_out, (orig_freq, new_freq, window, lowpass_filter_width, rolloff))
+    else:
+        y = _resample_rows(x3, orig_freq, new_freq, lengths, order, n_out, window, lowpass_filter_width, rolloff)
     return y.view(out_shape)
 
 
@@ -292,6 +336,9 @@ class StreamResampler:
     def push(self, samples: torch.Tensor, last: bool = False) -> torch.Tensor:
         if samples.ndim < 1:
             raise ValueError("push takes a (..., n_in) tensor")
+        if samples.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError("StreamResampler is not differentiable (whole signals only: use resample); there is no "
+                                      "operator fallback.")
         if not samples.is_cuda:
             raise _lib.EabError("StreamResampler needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
         lead = tuple(samples.shape[:-1])

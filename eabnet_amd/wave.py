@@ -9,7 +9,11 @@
 Two launches for the value, one for the gradient; ``grad_output`` is read on the device, nothing synchronises with the host.
 
 ``mr_stft_loss`` is the spectral half of a waveform objective -- spectral convergence plus log-magnitude distance at several
-time-frequency resolutions, csrc/spec_loss.hip -- added the same way: ``loss = loss + v * mr_stft_loss(wav, target)``."""
+time-frequency resolutions, csrc/spec_loss.hip -- added the same way: ``loss = loss + v * mr_stft_loss(wav, target)``.
+
+``stoi_loss`` trains for the two intelligibility scores ``Scorer(model, intelligibility=True)`` reports: minus a weighted sum of
+STOI and ESTOI, the value by the launches of ``intelligibility`` and the gradient by three more on the workspace they leave
+(csrc/stoi_bwd.hip); at 16 kHz it chains through the differentiable ``resample``."""
 from __future__ import annotations
 
 import ctypes as C
@@ -19,7 +23,8 @@ import torch
 
 from . import _lib
 from . import model as _m
-from .score import _lens, _row_args, _spans
+from .enhance import _rs
+from .score import STOI_RATE, _lens, _row_args, _spans
 
 REDUCTIONS = ("mean", "sum", "none")
 
@@ -295,3 +300,129 @@ def mr_stft_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, resolutio
     with torch.cuda.device(est.device):
         lens = _m._device_lengths(lens, est.device)
     return _MrStftLoss.apply(est_rows, clean_rows, lens, res, float(factor_sc), float(factor_mag), float(floor), reduction)
+
+
+class _StoiLoss(torch.autograd.Function):
+    """value: the five launches of eab_stoi_f32, unchanged, and the fp32 rounding of -(factor_stoi stoi + factor_estoi estoi) of its
+    fp64 scores; the workspace (window, twiddles, K, kept, band values) is kept for eab_stoi_bwd_f32, which reads grad_output on
+    the device"""
+
+    @staticmethod
+    def forward(ctx, est, clean, lens, factor_stoi, factor_estoi, reduction):
+        lib = _lib.load()
+        B = est.shape[0]
+        e, s = est.detach(), clean
+        cap = max(e.shape[1], s.shape[1])
+        nbytes = lib.eab_stoi_workspace_bytes(B, cap)
+        if nbytes < 0:
+            raise ValueError(f"stoi_loss takes at most 65535 rows of at most 2^30 samples, got {B} rows of {cap}")
+        with torch.cuda.device(e.device):
+            work = torch.empty((nbytes,), dtype=torch.uint8, device=e.device)
+            out = torch.empty((B, 2), dtype=torch.float64, device=e.device)
+            _lib.check(lib.eab_stoi_f32(*_row_args(B, e, s), lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), None, None,
+                                        None, _stream()), "eab_stoi_f32")
+            loss = -(factor_stoi * out[:, 0] + factor_estoi * out[:, 1])
+            if reduction != "none":
+                loss = loss.sum()
+                if reduction == "mean":
+                    loss = loss / B
+            loss = loss.to(torch.float32)
+        ctx.save_for_backward(e, lens, work)
+        ctx.cfg = (s.shape[1], factor_stoi, factor_estoi, reduction)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        e, lens, work = ctx.saved_tensors
+        clean_cap, factor_stoi, factor_estoi, reduction = ctx.cfg
+        lib = _lib.load()
+        B, L = e.shape
+        g = g.detach()
+        if g.dtype != torch.float32:
+            g = g.to(torch.float32)
+        per_row = reduction == "none"
+        gstride = g.stride(0) if per_row and B > 1 else 0
+        if gstride < 0:
+            g, gstride = g.contiguous(), 1
+        with torch.cuda.device(e.device):
+            nbytes = lib.eab_stoi_bwd_workspace_bytes(B, max(L, clean_cap))
+            scratch = torch.empty((nbytes,), dtype=torch.uint8, device=e.device)
+            grad = torch.empty((B, L), dtype=torch.float32, device=e.device)
+            _lib.check(lib.eab_stoi_bwd_f32(e.data_ptr(), e.stride(0) if B > 1 else L, L, clean_cap, lens.data_ptr(), B, work.data_ptr(),
+                                            work.numel(), factor_stoi, factor_estoi, g.data_ptr(), gstride,
+                                            1.0 / B if reduction == "mean" else 1.0, scratch.data_ptr(), nbytes, grad.data_ptr(), L,
+                                            _stream()), "eab_stoi_bwd_f32")
+        return grad, None, None, None, None, None
+
+
+def stoi_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, sample_rate: int = 16000, factor_stoi: float = 1.0,
+              factor_estoi: float = 0.0, reduction: str = "mean") -> torch.Tensor:
+    """Negative intelligibility of B utterances, differentiable with respect to ``est``: est (B, Le), clean (B, Ls) or (B, 1, Ls),
+    CUDA fp32 -> an fp32 scalar (``reduction`` "mean" or "sum") or (B,) ("none").
+
+        loss_b = -(factor_stoi * stoi_b + factor_estoi * estoi_b)
+
+    with both scores exactly those of ``intelligibility(est, clean, lengths, sample_rate)``: the value runs the
+    same launches and is the fp32 rounding of the same fp64 numbers.  The gradient is the literal derivative of
+    that definition with three conventions: the kept-frame set comes from ``clean`` alone and is a constant; a band value that
+    is exactly zero (every frame in est's zero tail) contributes no gradient; and where rule 9's bound binds an element it
+    contributes nothing through est, while ``alpha`` is differentiated on the others.  Fewer than 30 band frames give the
+    sentinel value -(factor_stoi + factor_estoi) 1e-5 and an exactly zero gradient.
+
+    lengths: None (the full rows), (B,) sample counts for both signals, or (B, 2) pairs (est, clean), as in ``si_sdr_loss``; a
+    signal counts as zero from its own length up to the longer of the two and is never read there, and the gradient is exactly
+    zero from est's length to the row's end.  sample_rate: 10000 runs on the rows as they are (strided rows are read in place);
+    any other rate resamples each signal with its OWN length as ``intelligibility`` does, est through the differentiable
+    ``resample``.  A zero factor skips that half's backward work.  Every sum has one fixed order: an utterance has the same
+    bits alone, in any batch and in a second call, value and gradient.  No double backward.  No operator fallback: CPU tensors,
+    other dtypes and a ``clean`` that requires grad raise."""
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    for name, v in (("factor_stoi", factor_stoi), ("factor_estoi", factor_estoi)):
+        if isinstance(v, bool) or not (isinstance(v, (int, float)) and 0.0 <= float(v) < float("inf")):
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+    if float(factor_stoi) == 0.0 and float(factor_estoi) == 0.0:
+        raise ValueError("factor_stoi and factor_estoi must not both be zero")
+    o, n = _rs._ratio(sample_rate, STOI_RATE)
+    if clean.ndim == 3 and clean.shape[1] == 1:
+        clean = clean[:, 0]
+    for name, t in (("est", est), ("clean", clean)):
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be a (B, L) tensor (clean may be (B, 1, L)), got {tuple(t.shape)}")
+    B = est.shape[0]
+    if clean.shape[0] != B:
+        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
+    if est.dtype != torch.float32 or clean.dtype != torch.float32:
+        raise TypeError(f"stoi_loss takes fp32 waves, got {est.dtype} and {clean.dtype} (there is no operator fallback)")
+    if clean.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("stoi_loss is differentiable with respect to est only: clean requires grad (detach it; "
+                                  "there is no operator fallback)")
+    widths = (est.shape[1], clean.shape[1])
+    if lengths is None:
+        cols = [[w] * B for w in widths]
+    else:
+        if isinstance(lengths, torch.Tensor):
+            pairs = lengths.ndim == 2
+            if pairs and tuple(lengths.shape) != (B, 2):
+                raise ValueError(f"lengths must have shape ({B},) or ({B}, 2), got {tuple(lengths.shape)}")
+            cols = [lengths[:, 0], lengths[:, 1]] if pairs else [lengths, lengths]
+        else:
+            rows = list(lengths)
+            pairs = len(rows) > 0 and all(isinstance(r, (list, tuple)) for r in rows)
+            if pairs and (len(rows) != B or any(len(r) != 2 for r in rows)):
+                raise ValueError(f"lengths must hold {B} counts or {B} (est, clean) pairs")
+            cols = [[r[0] for r in rows], [r[1] for r in rows]] if pairs else [rows, rows]
+        cols = [_m.check_lengths(c, B, w, lo=1, unit="the signal's row length", integral=True) for c, w in zip(cols, widths)]
+    if not (est.is_cuda and clean.is_cuda):
+        raise _lib.EabError("stoi_loss needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+    if est.device != clean.device:
+        raise ValueError("est and clean must be on one device")
+    est_rows, clean_rows = _rows_in_place(est), _rows_in_place(clean.detach())
+    if o != n:                                # as intelligibility: each signal with its own length, then the lengths at 10 kHz
+        est_rows, clean_rows = (_rs.resample(t, sample_rate, STOI_RATE, lengths=c) for t, c in zip((est_rows, clean_rows), cols))
+        cols = [(c.to(torch.int64) * n + (o - 1)) // o if isinstance(c, torch.Tensor) else [-(-n * v // o) for v in c]
+                for c in cols]
+    with torch.cuda.device(est.device):
+        lens = _lens(cols, B, est.device)
+    return _StoiLoss.apply(est_rows, clean_rows, lens, float(factor_stoi), float(factor_estoi), reduction)

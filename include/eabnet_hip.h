@@ -308,6 +308,30 @@ int eab_stoi_f32(const float* est, long long est_stride, int est_cap, const floa
                  float* tap_tob, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * The gradient of loss_b = -(factor_stoi stoi_b + factor_estoi estoi_b) with respect to est (csrc/stoi_bwd.hip):
+ * the literal derivative of §4.16 rules 2-10 with the kept-frame set constant (it comes from clean alone), zero through a band
+ * value that is exactly 0, and rule 9's clip differentiated on the branch each element took (alpha included).  Only entry
+ * points are added: EAB_ABI_VERSION stays 10.
+ *   est, lens, est_cap, clean_cap, B: those of the eab_stoi_f32 call that computed the value (the clean rows are not read again)
+ *   value_work  the `work` of that call, untouched since, called WITHOUT taps: it holds the window, the twiddles, K, kept
+ *           and the band values of both signals
+ *   factor_stoi, factor_estoi  >= 0, finite, not both 0 (a zero factor skips that half's work)
+ *   grad_out DEVICE float, one weight per utterance grad_out_stride >= 0 floats apart (0: one weight for all);  scale: a
+ *           host factor on all of them (1/B for a mean)
+ *   work    device scratch of eab_stoi_bwd_workspace_bytes(B, max(est_cap, clean_cap)) bytes, 16-byte aligned
+ *   grad    float rows of est_cap floats, grad_stride floats apart: grad_out[b] * scale * d loss_b / d est[b][i]; exactly 0 from
+ *           est's own length to est_cap, on samples that no kept frame covers or that lie past the last frame, and on the
+ *           whole row when fewer than 30 band frames remain
+ * Three launches, no host synchronisation, no atomics; every sum has one fixed order per utterance: a row has the same bits
+ * alone, in any batch, at any alignment and in a second call.
+ * ------------------------------------------------------------------------ */
+long long eab_stoi_bwd_workspace_bytes(int B, int cap);
+int eab_stoi_bwd_f32(const float* est, long long est_stride, int est_cap, int clean_cap, const int32_t* lens, int B,
+                     const void* value_work, long long value_work_bytes, double factor_stoi, double factor_estoi,
+                     const float* grad_out, int grad_out_stride, double scale, void* work, long long work_bytes, float* grad,
+                     long long grad_stride, eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * Sample-rate conversion of the rows of a padded batch (csrc/resample.hip).  Replaces, one file at a time on the host,
  * torchaudio.transforms.Resample(sr, 16000) of enhance.py:35-37 and test.py:65-68, and the microphone index_select of
  * enhance.py:41-42.  Only an entry point is added: EAB_ABI_VERSION stays 10.
@@ -330,6 +354,13 @@ int eab_stoi_f32(const float* est, long long est_stride, int est_cap, const floa
 int eab_resample_f32(const float* x, long long x_row_stride, int x_cols, const int32_t* row_map, const int32_t* in_lens, int rows,
                      int rows_per_utt, float* y, long long y_row_stride, int n_out, const float* tab, const int32_t* first, int o,
                      int n, int K, long long in_origin, long long out_origin, long long valid_hi, eab_stream_t stream);
+/* The adjoint of eab_resample_f32 on whole signals (both origins 0, no row map): for every input sample j < len
+ *     gx[j] = sum tab[p][k] * gy[q*n + p]   over the (q, p, k) with q*o + first[p] + k == j and q*n + p < min(n_out, ceil(n*len/o)),
+ * one gather per input sample in ascending output index, one fmaf per term; gx is exactly 0 from len to x_cols.
+ *   gy  [rows] rows of n_out floats, gy_row_stride apart;  gx  [rows] rows of x_cols floats, gx_row_stride apart;  in_lens as above */
+int eab_resample_bwd_f32(const float* gy, long long gy_row_stride, int n_out, const int32_t* in_lens, int rows, int rows_per_utt,
+                         float* gx, long long gx_row_stride, int x_cols, const float* tab, const int32_t* first, int o, int n,
+                         int K, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
  * Training mixtures of a padded batch: shoebox image-source rooms (csrc/room.hip).  Replaces, one sample at a time on the
