@@ -133,6 +133,7 @@ _SIGS = {
     "eab_room_gains_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_double, C.c_void_p, C.c_int, C.c_void_p,
                                                                                        C.c_void_p]),
     "eab_room_rirs_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_double, C.c_void_p, C.c_void_p]),
+    "eab_room_rirs_tail_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_double, C.c_void_p, C.c_void_p]),
     "eab_room_workspace_bytes": (C.c_longlong, [C.c_int] * 5),
     "eab_room_convolve_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int] * 2 + [C.c_void_p] * 2
                               + [C.c_longlong] + [C.c_void_p] * 3),

@@ -12,6 +12,12 @@
 //                         bits do not depend on which wave meets which image when.  One conversion to fp32, ordinary stores.
 //                         The 81 taps of an image are 81 lanes (tap i: lane i, and lanes 0..16 again for i >= 64): consecutive
 //                         LDS addresses.  sinc(i - 40 - f) = -(-1)^i sin(pi f) / (pi (i - 40 - f)): one sinf per image.
+// eab_room_rirs_tail_f32  the same table by the model "ism_tail" (DESIGN.md 4.23): of the images only those closer than
+//                         r_mix = c tail_start to the centre of the array, and from tail_start on a train of virtual images that
+//                         nothing stores: image j of source s is recomputed from four counter-based uniforms (arrival time at the
+//                         centre, direction, sign).  Their arrival times rise with j, so a segment's images are an index range,
+//                         computed from its bounds and the microphone's distance from the centre; the lanes run along j.  Both
+//                         parts add into the same integers: the bits do not depend on the schedule here either.
 // eab_room_convolve_f32   uniformly partitioned overlap-save, partition P = 512, 1024-point complex FFTs in LDS (fft_lds.h), three
 //                         launches: spectra of the source blocks x[(i-1)P, (i+1)P), spectra of the response partitions with TWO
 //                         channels per transform (h_c + i h_c', x is real: the product's real and imaginary parts are the two
@@ -41,7 +47,14 @@
 #define ROOM_C 343.0
 
 // scene record: [0..2] room, [3] absorption, [4] order, [5] sources, [6] reference microphone, [7] dBFS, [8 + j] snr_j,
-// [16 + 3 s + axis] source s, [40 + 3 m + axis] microphone m
+// [16 + 3 s + axis] source s, [40 + 3 m + axis] microphone m; read by room_rir_tail_kernel alone: [136] tail_seed,
+// [137] tail_start, [138] tail_density, [139] the scene's own K (it fixes the tail's images), [140] the sample its responses are cut at
+#define ROOM_TAIL_SEED 136
+#define ROOM_TAIL_START 137
+#define ROOM_TAIL_DENSITY 138
+#define ROOM_TAIL_K 139
+#define ROOM_TAIL_CUT 140
+#define ROOM_MAX_DENSITY 64
 __device__ __forceinline__ int room_int(double v, int lo, int hi) {
     const double c = fmin(fmax(v, (double)lo), (double)hi);        // (NaN -> lo)
     return (int)c;
@@ -51,7 +64,7 @@ extern __shared__ __attribute__((aligned(16))) unsigned char room_lds[];
 
 // more than 64 KB of dynamic LDS needs the function attribute: set once per device and entry point, not on every call
 static hipError_t room_large_lds(const void* const* fns, int n, int entry) {
-    static bool done[2][64];
+    static bool done[3][64];
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
@@ -258,6 +271,194 @@ extern "C" int eab_room_rirs_f32(const double* scenes, int B, int S_max, int M, 
     hipError_t e = room_large_lds(&fn, 1, 0);
     if (e != hipSuccess) return eab_hip_status(e);
     hipLaunchKernelGGL(room_rir_kernel, dim3((unsigned)((K + ROOM_SEG - 1) / ROOM_SEG), (unsigned)(M + 1), (unsigned)(B * S_max)),
+                       dim3(ROOM_THREADS), lds, eab_stream(stream), scenes, fs, S_max, M, K, h);
+    EAB_RETURN_LAUNCH_STATUS();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// impulse responses, "ism_tail": the images near the array and a sampled tail
+struct RoomTaps {                             // what a lane knows of its taps i = lane and lane + 64 (room_rir_kernel has the same values)
+    float hann0, hann1, sgn, x0, x1;
+    int lane;
+};
+
+// the pulses of the lanes that `keep`, one after the other (the whole wave calls this): gain g, delay krel + f against the
+// segment's first sample; taps at and past `cut` are dropped.  The arithmetic of a tap is room_rir_kernel's.
+__device__ __forceinline__ void room_add_pulses(unsigned long long* acc, int cut, bool keep, int krel, float g, float ff,
+                                                const RoomTaps& tp) {
+    unsigned long long mask = __ballot(keep);
+    if (!mask) return;
+    const float pi_f = 3.14159265358979323846f;
+    const float a = g * sinf(pi_f * (ff > 0.5f ? 1.0f - ff : ff)) / pi_f;              // g sin(pi f) / pi
+    while (mask) {
+        const int src = __ffsll((long long)mask) - 1;
+        mask &= mask - 1;
+        const int kk = __shfl(krel, src, 64);
+        const float gg = __shfl(g, src, 64), aa = __shfl(a, src, 64), fr = __shfl(ff, src, 64);
+        {
+            const float xx = tp.x0 - fr;
+            const float v = tp.hann0 * (xx == 0.0f ? gg : tp.sgn * aa / xx);
+            const int t = kk + tp.lane;
+            if (t >= 0 && t < cut) atomicAdd(&acc[t], (unsigned long long)llrintf(v * 1099511627776.0f));
+        }
+        if (tp.lane < ROOM_TAPS - 64) {
+            const float xx = tp.x1 - fr;
+            const float v = tp.hann1 * (tp.sgn * aa / xx);
+            const int t = kk + tp.lane + 64;
+            if (t >= 0 && t < cut) atomicAdd(&acc[t], (unsigned long long)llrintf(v * 1099511627776.0f));
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned long long room_mix64(unsigned long long z) {
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+
+// uniform d (0..3) of image j of source s, in [0, 1)
+__device__ __forceinline__ double room_uniform(unsigned long long seed, int s, int d, int j) {
+    const unsigned long long counter = ((unsigned long long)(4 * s + d) << 32) | (unsigned long long)(unsigned int)j;
+    return (double)(room_mix64(seed + 0x9E3779B97F4A7C15ull * (1ull + counter)) >> 11) * 1.1102230246251565e-16;   // 2^-53
+}
+
+// the orders n whose image can lie closer than r to the coordinate c: the image of n lies in [n L, (n + 1) L] for a source
+// inside the room.  One order of slack either side; every image is tested exactly afterwards.
+__device__ __forceinline__ void room_orders(double c, double r, double L, int O, int* lo, int* hi) {
+    *lo = room_int(floor((c - r) / L) - 1.0, -O, O);
+    *hi = room_int(floor((c + r) / L) + 1.0, -O, O);
+}
+
+__global__ __launch_bounds__(ROOM_THREADS) void room_rir_tail_kernel(const double* __restrict__ scenes, double fs, int S_max, int M,
+                                                                     int K, float* __restrict__ h) {
+    unsigned long long* acc = reinterpret_cast<unsigned long long*>(room_lds);          // [ROOM_SEG]
+    float* beta = reinterpret_cast<float*>(room_lds + sizeof(unsigned long long) * ROOM_SEG);   // [ROOM_MAX_ORDER + 1]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int seg0 = blockIdx.x * ROOM_SEG, m = blockIdx.y, bs = blockIdx.z, b = bs / S_max, s = bs - b * S_max;
+    const int seglen = min(ROOM_SEG, K - seg0);
+    const double* sc = scenes + (long long)b * ROOM_SCENE;
+    float* hr = h + ((long long)bs * (M + 1) + m) * K + seg0;
+    const int S = room_int(sc[5], 1, S_max);
+    const int cut = max(0, min(seglen, room_int(sc[ROOM_TAIL_CUT], 1, K) - seg0));     // the scene's responses end inside this segment
+    if (s >= S || cut == 0) {                                          // (workgroup-uniform) a row nobody reads, or past the end: zeros
+        for (int t = tid; t < seglen; t += ROOM_THREADS) hr[t] = 0.0f;
+        return;
+    }
+    const bool free_row = m == M;                                      // row M: the free-field response, the image n = 0 alone
+    const int O = free_row ? 0 : room_int(sc[4], 0, ROOM_MAX_ORDER);
+    const int mic = free_row ? room_int(sc[6], 0, M - 1) : m;
+    const double Lx = sc[0], Ly = sc[1], Lz = sc[2];
+    const double sx = sc[16 + 3 * s], sy = sc[17 + 3 * s], sz = sc[18 + 3 * s];
+    const double rx = sc[40 + 3 * mic], ry = sc[41 + 3 * mic], rz = sc[42 + 3 * mic];
+    double cx = 0.0, cy = 0.0, cz = 0.0;                               // the centre of the array: the microphones in index order
+    for (int q = 0; q < M; ++q) {
+        cx += sc[40 + 3 * q];
+        cy += sc[41 + 3 * q];
+        cz += sc[42 + 3 * q];
+    }
+    cx /= (double)M, cy /= (double)M, cz /= (double)M;
+    const double t_start = fmin(fmax(sc[ROOM_TAIL_START], 0.0), 1.0e6);                // (NaN -> 0)
+    const double r_mix = ROOM_C * t_start;
+    for (int t = tid; t < seglen; t += ROOM_THREADS) acc[t] = 0ull;
+    for (int k = tid; k <= O; k += ROOM_THREADS) beta[k] = (float)pow(1.0 - sc[3], 0.5 * (double)k);
+    __syncthreads();
+
+    RoomTaps tp;
+    tp.hann0 = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)lane / 80.0));
+    tp.hann1 = (float)(0.5 - 0.5 * cos(2.0 * M_PI * (double)(lane + 64) / 80.0));
+    tp.sgn = (lane & 1) ? 1.0f : -1.0f;                                // -(-1)^i, the same for i and i + 64
+    tp.x0 = (float)(lane - 40), tp.x1 = (float)(lane + 24);
+    tp.lane = lane;
+    const float pi_f = 3.14159265358979323846f;
+
+    // the early part: the lattice walk of room_rir_kernel over the orders that can lie inside the sphere of r_mix about the centre
+    int nxl, nxh, nyl, nyh, nzl, nzh;
+    room_orders(cx, r_mix, Lx, O, &nxl, &nxh);
+    room_orders(cy, r_mix, Ly, O, &nyl, &nyh);
+    room_orders(cz, r_mix, Lz, O, &nzl, &nzh);
+    const int W = max(0, nxh - nxl + 1), H = max(0, nyh - nyl + 1);
+    for (int col = wave; col < W * H; col += ROOM_THREADS / 64) {        // (everything but the lanes' nz is wave-uniform)
+        const int nx = nxl + col / H, ny = nyl + col % H;
+        const int rem = O - abs(nx) - abs(ny);
+        if (rem < 0) continue;
+        const double px = room_image(nx, Lx, sx), py = room_image(ny, Ly, sy);
+        const double ex = px - cx, ey = py - cy;
+        const double exy2 = ex * ex + ey * ey;
+        if (!free_row && !(sqrt(exy2) < r_mix)) continue;              // the column's nearest image lies beyond r_mix
+        const double dx = px - rx, dy = py - ry;
+        const double dxy2 = dx * dx + dy * dy;
+        if (fmin(sqrt(dxy2) * fs / ROOM_C, 2.0e9) >= (double)(seg0 + cut)) continue;    // the whole column arrives later
+        const int zl = max(-rem, nzl), zh = min(rem, nzh);
+        for (int nz0 = zl; nz0 <= zh; nz0 += 64) {
+            const int nz = nz0 + lane;
+            const double pz = room_image(nz, Lz, sz);
+            const double dz = pz - rz, ez = pz - cz;
+            const double d = sqrt(dxy2 + dz * dz);
+            const double tau = fmin(d * fs / ROOM_C, 2.0e9);
+            const double fl = floor(tau);
+            const int k0 = (int)fl;
+            const bool inside = free_row || sqrt(exy2 + ez * ez) < r_mix;                // the test on the centre: one image set for all microphones
+            const bool keep = nz <= zh && inside && k0 + (ROOM_TAPS - 1) >= seg0 && k0 < seg0 + cut && d > 0.0;
+            const float g = beta[min(abs(nx) + abs(ny) + abs(nz), O)] / (4.0f * pi_f * (float)d);
+            room_add_pulses(acc, cut, keep, k0 - seg0, g, (float)(tau - fl), tp);
+        }
+    }
+
+    // the tail: J virtual images spread over the n_slots samples from tail_start to the scene's own K - ROOM_TAPS
+    const double k_mix = fmin(floor(t_start * fs), 2.0e9);
+    const double n_slots = (double)room_int(sc[ROOM_TAIL_K], 1, ROOM_MAX_K) - (double)ROOM_TAPS - k_mix;
+    const double density = fmin(fmax(sc[ROOM_TAIL_DENSITY], 0.0), (double)ROOM_MAX_DENSITY);
+    const double absorb = fmax(sc[3], 0.0);
+    if (!free_row && n_slots > 0.0 && absorb < 1.0 && density > 0.0) { // (workgroup-uniform)
+        const int J = (int)ceil(density * n_slots);                    // <= 64 * 2^22
+        const double nu = (double)J / n_slots;
+        const double ex = rx - cx, ey = ry - cy, ez = rz - cz;
+        const double rho = sqrt(ex * ex + ey * ey + ez * ez) * fs / ROOM_C;            // |tau - fs t_j| <= rho: the triangle inequality
+        // image j reaches the centre (j + U0) / nu samples after tail_start: those that can reach [seg0 - 80, seg0 + cut), one
+        // sample and one image of slack either side; each is tested exactly below
+        const double first = ((double)seg0 - (double)(ROOM_TAPS - 1) - rho - t_start * fs - 1.0) * nu;
+        const double last = ((double)(seg0 + cut) + rho - t_start * fs + 1.0) * nu;
+        const int jlo = room_int(floor(first) - 1.0, 0, J), jhi = room_int(floor(last) + 1.0, -1, J - 1);
+        const unsigned long long seed = (unsigned long long)fmin(fmax(sc[ROOM_TAIL_SEED], 0.0), 9007199254740991.0);
+        const double half_ln = 0.5 * log(1.0 - absorb);
+        const double V = Lx * Ly * Lz;
+        for (int j0 = jlo + wave * 64; j0 <= jhi; j0 += ROOM_THREADS) {                // (wave-uniform) the lanes along j
+            const int j = j0 + lane;
+            const double u0 = room_uniform(seed, s, 0, j), u1 = room_uniform(seed, s, 1, j);
+            const double u2 = room_uniform(seed, s, 2, j), u3 = room_uniform(seed, s, 3, j);
+            const double t = t_start + ((double)j + u0) / (nu * fs);
+            const double z = 2.0 * u1 - 1.0;
+            const double r = sqrt(fmax(1.0 - z * z, 0.0));
+            double sn, cs;
+            sincospi(2.0 * u2, &sn, &cs);
+            const double ux = r * cs, uy = r * sn, ct = ROOM_C * t;
+            const double dx = (cx + ct * ux) - rx, dy = (cy + ct * uy) - ry, dz = (cz + ct * z) - rz;
+            const double d = sqrt(dx * dx + dy * dy + dz * dz);
+            const double tau = fmin(d * fs / ROOM_C, 2.0e9);
+            const double fl = floor(tau);
+            const int k0 = (int)fl;
+            const bool keep = j <= jhi && k0 + (ROOM_TAPS - 1) >= seg0 && k0 < seg0 + cut && d > 0.0;
+            if (!__ballot(keep)) continue;
+            const double walls = ct * (fabs(ux) / Lx + fabs(uy) / Ly + fabs(z) / Lz);  // this image's own reflection count
+            const double g = sqrt(4.0 * M_PI * ROOM_C * ROOM_C * ROOM_C * t * t / (V * fs * nu)) * exp(walls * half_ln) / (4.0 * M_PI * d);
+            room_add_pulses(acc, cut, keep, k0 - seg0, (float)(u3 < 0.5 ? -g : g), (float)(tau - fl), tp);
+        }
+    }
+    __syncthreads();
+    for (int t = tid; t < seglen; t += ROOM_THREADS)
+        hr[t] = t < cut ? (float)((double)(long long)acc[t] * 9.094947017729282e-13) : 0.0f;   // 2^-40
+}
+
+extern "C" int eab_room_rirs_tail_f32(const double* scenes, int B, int S_max, int M, int K, double fs, float* h, eab_stream_t stream) {
+    EAB_CHECK_ARG(scenes && h);
+    EAB_CHECK_ARG(B >= 1 && B <= 4096 && S_max >= 1 && S_max <= ROOM_MAX_SRC && M >= 1 && M <= ROOM_MAX_MIC);
+    EAB_CHECK_ARG(K >= 1 && K <= ROOM_MAX_K && fs >= 10.0 && fs <= 1.0e7);
+    const size_t lds = sizeof(unsigned long long) * ROOM_SEG + sizeof(float) * (ROOM_MAX_ORDER + 1);
+    const void* fn = reinterpret_cast<const void*>(&room_rir_tail_kernel);
+    hipError_t e = room_large_lds(&fn, 1, 2);
+    if (e != hipSuccess) return eab_hip_status(e);
+    hipLaunchKernelGGL(room_rir_tail_kernel, dim3((unsigned)((K + ROOM_SEG - 1) / ROOM_SEG), (unsigned)(M + 1), (unsigned)(B * S_max)),
                        dim3(ROOM_THREADS), lds, eab_stream(stream), scenes, fs, S_max, M, K, h);
     EAB_RETURN_LAUNCH_STATUS();
 }

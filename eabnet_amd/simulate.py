@@ -16,6 +16,10 @@ int(fs/10) samples above -50 dB), the mixture scaled to dBFS.  Then
 
     noisy[m][t] = sum_s gain_s (x_s * h[s][m])[t],        clean[t] = gain_0 (x_0 * h_free[0][ref])[t],        t < L_b.
 
+``rir_method="ism_tail"`` keeps of these images the ones closer than c tail_start to the centre of the array and
+replaces the rest by a sampled tail: tail_density virtual images per sample with random directions and signs, recomputed on the
+device from tail_seed; what it approximates is the ``"ism"`` response above, at about a tenth of its pulses.
+
 The ``"hybrid"`` method of the reference's settings files (stochastic ray tracing, air absorption) is refused.  Reading,
 cropping and resampling the source files stays with the caller (``eabnet_amd.resample``).  ``sample_scene`` is host code; the
 rest runs on the device and has no CPU fallback."""
@@ -43,6 +47,9 @@ PARTITION = 512                               # ROOM_PART
 NFFT = 1024                                   # ROOM_NFFT
 GAIN_SUMS = 44                                # ROOM_NQ: doubles per window of the gains' scratch (36 Gram entries, 8 peaks)
 MIN_SOURCE_MIC_DISTANCE = 0.1
+RIR_METHODS = ("ism", "ism_tail")
+MAX_TAIL_DENSITY = 64.0                       # ROOM_MAX_DENSITY
+MIN_TAIL_DISTANCE = 1.0                       # metres between the array and the nearest virtual image of the tail
 _TWIDDLES: Dict[str, torch.Tensor] = {}
 
 
@@ -87,6 +94,9 @@ class Scene:
     rt60: Optional[float] = None
     clean_name: Optional[str] = None
     meta: dict = field(default_factory=dict)
+    tail_start: float = 0.05                  # "ism_tail": seconds from which the sampled tail stands for the images
+    tail_density: float = 2.0                 # "ism_tail": virtual images per sample; 0: no tail
+    tail_seed: int = 0                        # "ism_tail": an integer in [0, 2^53)
 
     @property
     def n_sources(self) -> int:
@@ -99,9 +109,9 @@ class Scene:
 
 def check_scene(sc: Scene) -> None:
     """the refusals of the module: ValueError on the host, before anything is launched"""
-    if sc.rir_method != "ism":
-        raise ValueError(f"rir_method {sc.rir_method!r} is not supported: only the image-source model 'ism' is (the 'hybrid' "
-                         "method adds stochastic ray tracing and air absorption)")
+    if sc.rir_method not in RIR_METHODS:
+        raise ValueError(f"rir_method {sc.rir_method!r} is not supported: only the image-source model 'ism' and its variant with a "
+                         "sampled tail 'ism_tail' are (the 'hybrid' method adds stochastic ray tracing and air absorption)")
     Lr = np.asarray(sc.room_dim, dtype=np.float64)
     src = np.asarray(sc.sources, dtype=np.float64)
     mic = np.asarray(sc.mics, dtype=np.float64)
@@ -135,6 +145,30 @@ def check_scene(sc: Scene) -> None:
     if dist.min() < MIN_SOURCE_MIC_DISTANCE:
         s, m = np.unravel_index(int(dist.argmin()), dist.shape)
         raise ValueError(f"source {s} lies {dist.min():.3f} m from microphone {m}: closer than {MIN_SOURCE_MIC_DISTANCE} m")
+    if sc.rir_method == "ism_tail":
+        _check_tail(sc.tail_start, sc.tail_density)
+        seed = sc.tail_seed
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 53:
+            raise ValueError(f"tail_seed must be an integer in [0, 2^53) (a double holds it exactly), got {seed!r}")
+        radius = array_radius(mic)
+        if SOUND_SPEED * float(sc.tail_start) < MIN_TAIL_DISTANCE + radius:
+            raise ValueError(f"the tail would start too close to the array: c tail_start = {SOUND_SPEED * float(sc.tail_start):.3f} m is "
+                             f"below {MIN_TAIL_DISTANCE} m plus the array's radius of {radius:.3f} m")
+
+
+def _check_tail(tail_start, tail_density) -> None:
+    if not (math.isfinite(float(tail_start)) and float(tail_start) > 0.0):
+        raise ValueError(f"tail_start must be a positive number of seconds, got {tail_start}")
+    if not (math.isfinite(float(tail_density)) and float(tail_density) >= 0.0):
+        raise ValueError(f"tail_density must be finite and not negative, got {tail_density}")
+    if float(tail_density) > MAX_TAIL_DENSITY:
+        raise ValueError(f"tail_density is at most {MAX_TAIL_DENSITY:g} virtual images per sample, got {tail_density}")
+
+
+def array_radius(mics) -> float:
+    """the largest distance of a microphone from the mean of the microphone positions"""
+    mic = np.asarray(mics, dtype=np.float64)
+    return float(np.sqrt(((mic - mic.mean(0)) ** 2).sum(-1)).max())
 
 
 def _angle_deg(v1, v2) -> float:
@@ -147,13 +181,15 @@ def _uniform(rng: np.random.Generator, bounds) -> float:
 
 
 def sample_scene(settings: dict, rng: np.random.Generator, clean_name: Optional[str] = None, rir_method: Optional[str] = None,
-                 max_tries: int = 100000) -> Scene:
+                 max_tries: int = 100000, tail_start: float = 0.05, tail_density: float = 2.0) -> Scene:
     """one random scene by the rules of a settings dictionary (the reference's mcse_dataset_settings*.json): room between
     min_dim and max_dim; target and array centre at their heights, away from the walls, at a distance inside
     target.dist_to_mic_array (drawn again together otherwise); the array rotated about the vertical so that its direction
     points at the target; noise.n[0]..n[1] noises anywhere in the room at their heights, at least min_dist_to_mic_array from
     the array's centre and min_doa_diff_wrt_target degrees off the target as seen from it (each drawn again otherwise); one SNR
-    per noise; an rt60 that the room can have (drawn again otherwise); dBFS.  rir_method overrides the settings' own."""
+    per noise; an rt60 that the room can have (drawn again otherwise); dBFS.  rir_method overrides the settings' own; for
+    "ism_tail" the scene gets tail_start and tail_density and, as the generator's last draw, its tail_seed (no other method
+    draws it: their scenes of a given seed do not change)."""
     room = settings["room"]
     lo, hi = np.asarray(room["min_dim"], dtype=np.float64), np.asarray(room["max_dim"], dtype=np.float64)
     room_dim = lo + (hi - lo) * rng.random(3)
@@ -202,22 +238,30 @@ def sample_scene(settings: dict, rng: np.random.Generator, clean_name: Optional[
         break
     else:
         raise ValueError("no rt60 of the settings fits the room")
-    return Scene(room_dim=room_dim, absorption=a, max_order=order, fs=settings["audio"]["fs"], sources=np.stack(sources), mics=mics,
-                 ref_mic=int(arr["ref_mic"]), snr=snr, dBFS=_uniform(rng, settings["noisy_dBFS"]),
-                 rir_method=rir_method if rir_method is not None else settings["audio"]["rir_method"], rt60=rt60,
-                 clean_name=clean_name, meta={"array_centre": centre})
+    sc = Scene(room_dim=room_dim, absorption=a, max_order=order, fs=settings["audio"]["fs"], sources=np.stack(sources), mics=mics,
+               ref_mic=int(arr["ref_mic"]), snr=snr, dBFS=_uniform(rng, settings["noisy_dBFS"]),
+               rir_method=rir_method if rir_method is not None else settings["audio"]["rir_method"], rt60=rt60,
+               clean_name=clean_name, meta={"array_centre": centre})
+    if sc.rir_method == "ism_tail":
+        sc.tail_start, sc.tail_density = float(tail_start), float(tail_density)
+        sc.tail_seed = int(rng.integers(0, 1 << 53))
+    return sc
 
 
 # -------------------------------------------------------------------------------------------------------------------------------
 # the device side
-def _scene_record(sc: Scene) -> np.ndarray:
-    """the SCENE_DOUBLES doubles csrc/room.hip reads for one scene"""
+def _scene_record(sc: Scene, k: Optional[int] = None) -> np.ndarray:
+    """the SCENE_DOUBLES doubles csrc/room.hip reads for one scene; k: the sample its responses are cut at ("ism_tail" alone
+    reads it; default: the scene's own response length)"""
     r = np.zeros(SCENE_DOUBLES, dtype=np.float64)
     r[0:3] = np.asarray(sc.room_dim, dtype=np.float64)
     r[3], r[4], r[5], r[6], r[7] = sc.absorption, sc.max_order, sc.n_sources, sc.ref_mic, sc.dBFS
     r[9:9 + sc.n_sources - 1] = np.asarray(sc.snr, dtype=np.float64)
     r[16:16 + 3 * sc.n_sources] = np.asarray(sc.sources, dtype=np.float64).reshape(-1)
     r[40:40 + 3 * sc.n_mics] = np.asarray(sc.mics, dtype=np.float64).reshape(-1)
+    if sc.rir_method == "ism_tail":
+        own = rir_length(sc.room_dim, sc.max_order, sc.fs)
+        r[136:141] = sc.tail_seed, sc.tail_start, sc.tail_density, own, own if k is None else k
     return r
 
 
@@ -230,6 +274,8 @@ def _check_batch(scenes: Sequence[Scene], S_max: Optional[int] = None) -> Tuple[
     fs, M = float(scenes[0].fs), scenes[0].n_mics
     if any(float(sc.fs) != fs or sc.n_mics != M for sc in scenes):
         raise ValueError("the scenes of one batch share the sample rate and the number of microphones")
+    if any(sc.rir_method != scenes[0].rir_method for sc in scenes):
+        raise ValueError("the scenes of one batch share the rir_method: one launch makes all their responses")
     most = max(sc.n_sources for sc in scenes)
     if S_max is None:
         S_max = most
@@ -256,6 +302,8 @@ def first_arrival(sc: Scene) -> int:
     definition's value there is zero, so this is a property of this implementation, not part of the contract."""
     src, mic = np.asarray(sc.sources, dtype=np.float64), np.asarray(sc.mics, dtype=np.float64)
     d = np.sqrt(((src[:, None, :] - mic[None, :, :]) ** 2).sum(-1)).min()
+    if sc.rir_method == "ism_tail":                                   # the tail's images lie c tail_start or more from the centre
+        d = min(d, SOUND_SPEED * float(sc.tail_start) - array_radius(mic))
     return max(0, int(math.floor(d * float(sc.fs) / SOUND_SPEED)) - 1)
 
 
@@ -297,8 +345,9 @@ def _check_sources(sources: torch.Tensor, scenes: Sequence[Scene], lengths):
     return sources, fs, M, lens
 
 
-def _launch_rirs(records: torch.Tensor, B: int, S_max: int, M: int, K: int, fs: float, h: torch.Tensor) -> None:
-    _lib.check(_lib.load().eab_room_rirs_f32(records.data_ptr(), B, S_max, M, K, fs, h.data_ptr(), _stream()), "eab_room_rirs_f32")
+def _launch_rirs(records: torch.Tensor, B: int, S_max: int, M: int, K: int, fs: float, h: torch.Tensor, method: str = "ism") -> None:
+    name = {"ism": "eab_room_rirs_f32", "ism_tail": "eab_room_rirs_tail_f32"}[method]
+    _lib.check(getattr(_lib.load(), name)(records.data_ptr(), B, S_max, M, K, fs, h.data_ptr(), _stream()), name)
 
 
 def _launch_gains(x: torch.Tensor, lens: torch.Tensor, records: torch.Tensor, fs: float, partial: torch.Tensor, nwin: int,
@@ -317,16 +366,17 @@ def image_source_rirs(scenes: Sequence[Scene], device, max_rir_seconds: Optional
     """(h, lengths): h (B, S, M + 1, K) fp32 on ``device``, h[b, s, m] the response from source s to microphone m and
     h[b, s, M] the free-field response to the reference microphone; K the longest of the scenes' own response lengths
     ``lengths`` (rows are zero past them, and for s >= S_b).  max_rir_seconds (a deviation, off by default): responses are cut
-    at that many seconds; images that arrive later are dropped.  sources: rows S of the table (default: the most of any scene)."""
+    at that many seconds; images that arrive later are dropped.  sources: rows S of the table (default: the most of any scene).
+    The scenes' rir_method picks the model: "ism", or "ism_tail" (the tail's images are those of the uncut response)."""
     device = torch.device(device)
     fs, M, S_max = _check_batch(scenes, sources)
     _need_cuda(device, "image_source_rirs")
     ks = response_lengths(scenes, max_rir_seconds)
     K, B = max(ks), len(scenes)
     with torch.cuda.device(device):
-        records = _to_device(np.stack([_scene_record(sc) for sc in scenes]), device)
+        records = _to_device(np.stack([_scene_record(sc, k) for sc, k in zip(scenes, ks)]), device)
         h = torch.empty((B, S_max, M + 1, K), dtype=torch.float32, device=device)
-        _launch_rirs(records, B, S_max, M, K, fs, h)
+        _launch_rirs(records, B, S_max, M, K, fs, h, scenes[0].rir_method)
     return h, ks
 
 
@@ -367,7 +417,7 @@ def _simulate(sources: torch.Tensor, scenes: Sequence[Scene], lengths, max_rir_s
     if work_bytes < 0:
         raise ValueError(f"simulate_rooms: shape (B, S, M, L, K) = {(B, S_max, M, L, K)} is out of the kernels' range")
     with torch.cuda.device(dev):
-        records = _to_device(np.stack([_scene_record(sc) for sc in scenes]), dev)
+        records = _to_device(np.stack([_scene_record(sc, k) for sc, k in zip(scenes, ks)]), dev)
         dlens = _m._device_lengths(lens, dev)
         klen = _to_device(np.asarray([[k, first_arrival(sc)] for k, sc in zip(ks, scenes)], dtype=np.int32), dev)
         nwin = _windows(L, fs)
@@ -381,7 +431,7 @@ def _simulate(sources: torch.Tensor, scenes: Sequence[Scene], lengths, max_rir_s
         else:
             noisy, clean = out
         _launch_gains(sources, dlens, records, fs, partial, nwin, gains)
-        _launch_rirs(records, B, S_max, M, K, fs, h)
+        _launch_rirs(records, B, S_max, M, K, fs, h, scenes[0].rir_method)
         _lib.check(lib.eab_room_convolve_f32(sources.data_ptr(), B, S_max, L, dlens.data_ptr(), records.data_ptr(), klen.data_ptr(),
                                              gains.data_ptr(), h.data_ptr(), M, K, _twiddles(dev).data_ptr(), work.data_ptr(),
                                              work_bytes, noisy.data_ptr(), clean.data_ptr(), _stream()), "eab_room_convolve_f32")
@@ -404,12 +454,15 @@ class RoomSimulator:
     host synchronisation.  Two output slots alternate: the tensors of a call stay untouched until the call after the next."""
 
     def __init__(self, settings: dict, max_batch: int = 6, seed: int = 0, rir_method: Optional[str] = None,
-                 max_rir_seconds: Optional[float] = None):
+                 max_rir_seconds: Optional[float] = None, tail_start: float = 0.05, tail_density: float = 2.0):
         self.settings = settings
         self.rir_method = rir_method if rir_method is not None else settings["audio"]["rir_method"]
-        if self.rir_method != "ism":
-            raise ValueError(f"rir_method {self.rir_method!r} is not supported: only the image-source model 'ism' is; pass "
-                             "rir_method='ism' to use a settings file written for 'hybrid'")
+        if self.rir_method not in RIR_METHODS:
+            raise ValueError(f"rir_method {self.rir_method!r} is not supported: only the image-source model 'ism' and its variant "
+                             "with a sampled tail 'ism_tail' are; pass rir_method='ism' or rir_method='ism_tail' to use a settings "
+                             "file written for 'hybrid'")
+        _check_tail(tail_start, tail_density)
+        self.tail_start, self.tail_density = float(tail_start), float(tail_density)
         if len(settings["mic_array"]["mics"]) > MAX_MICS:
             raise ValueError(f"a scene has at most {MAX_MICS} microphones, got M = {len(settings['mic_array']['mics'])}")
         if settings["noise"]["n"][1] + 1 > MAX_SOURCES:
@@ -429,8 +482,8 @@ class RoomSimulator:
     def sample(self, n: int, clean_names: Optional[Sequence[str]] = None) -> List[Scene]:
         if not 1 <= n <= self.max_batch:
             raise ValueError(f"a batch has 1 to max_batch = {self.max_batch} scenes, got {n}")
-        return [sample_scene(self.settings, self.rng, None if clean_names is None else clean_names[i], rir_method=self.rir_method)
-                for i in range(n)]
+        return [sample_scene(self.settings, self.rng, None if clean_names is None else clean_names[i], rir_method=self.rir_method,
+                             tail_start=self.tail_start, tail_density=self.tail_density) for i in range(n)]
 
     def simulate(self, sources: torch.Tensor, scenes: Sequence[Scene], lengths=None):
         if len(scenes) > self.max_batch:

@@ -380,6 +380,12 @@ int eab_resample_bwd_f32(const float* gy, long long gy_row_stride, int n_out, co
  * eab_room_rirs_f32: h [B][S_max][M+1][K] fp32, row M the free-field response of the reference microphone (zeros for
  *   s >= S_b).  Geometry in fp64, taps in fp32, summed as rint(tap * 2^40) in 64-bit integers: bits independent of scheduling.
  *   A pulse is cut at K.  One launch.
+ * eab_room_rirs_tail_f32: the same table by the model "ism_tail" of DESIGN.md §4.23: the images closer than c tail_start to
+ *   the mean of the microphone positions, and from tail_start on ceil(tail_density n_slots) virtual images recomputed from a
+ *   counter-based generator.  It reads five more slots of the scene record, which the other entry points ignore: [136]
+ *   tail_seed (an integer below 2^53), [137] tail_start in seconds, [138] tail_density (clamped to [0, 64]), [139] the scene's
+ *   own response length (it fixes the tail's images), [140] the sample the scene's responses are cut at (clamped to [1, K];
+ *   zeros from there on).  Same accumulation, same determinism, one launch.
  * eab_room_convolve_f32: noisy [B][M][L] = sum_s gains[s] (x_s * h[s][m]), clean [B][L] = gains[0] (x_0 * h[0][M]), zero from
  *   lens[b] on.  twiddle: DEVICE float [1024][2], exp(-2 pi i j / 1024); work: eab_room_workspace_bytes bytes, 16-byte
  *   aligned.  Three launches; an utterance has the same bits alone, in any batch and in a second call.
@@ -387,6 +393,7 @@ int eab_resample_bwd_f32(const float* gy, long long gy_row_stride, int n_out, co
 int eab_room_gains_f32(const float* x, int B, int S_max, int L, const int32_t* lens, const double* scenes, double fs,
                        double* partial, int partial_windows, double* gains, eab_stream_t stream);
 int eab_room_rirs_f32(const double* scenes, int B, int S_max, int M, int K, double fs, float* h, eab_stream_t stream);
+int eab_room_rirs_tail_f32(const double* scenes, int B, int S_max, int M, int K, double fs, float* h, eab_stream_t stream);
 long long eab_room_workspace_bytes(int B, int S_max, int M, int L, int K);
 int eab_room_convolve_f32(const float* x, int B, int S_max, int L, const int32_t* lens, const double* scenes, const int32_t* klen,
                           const double* gains, const float* h, int M, int K, const float* twiddle, void* work,

@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """Room simulation on the device: the three entry points of csrc/room.hip on the training workload.
 
-    python tools/bench_simulate.py [--reps 5] [--train-step-ms MS] [--no-host | --host-only] [--out profiles/simulate_bench.json]
+    python tools/bench_simulate.py [--reps 5] [--method ism|ism_tail|both] [--train-step-ms MS] [--no-host | --host-only]
+                                   [--out profiles/simulate_bench.json]
 
 Workload: B = 6 utterances of 6 s at 16 kHz, the 8 microphones of the v3 array (tests/golden/mcse_dataset_settings_v3.json),
 1 target + 4 noises per scene.  "settings": rooms and rt60 drawn from the settings with fixed seeds.  "worst": the same draws
 with rt60 = 0.7 s for every scene (image orders 79 to 95, 0.7 to 1.2 million images per response).  Per entry point (gains,
 impulse responses, convolution): ``reps`` back-to-back calls between two HIP events, best of three, in ms per batch; "all" is
-``simulate_rooms`` as a whole (uploads of the scene records included).
+``simulate_rooms`` as a whole (uploads of the scene records included).  --method picks the response model (DESIGN.md 4.18,
+4.23); "both" times "ism" and "ism_tail" on the same draws in one session and nests the rows under the method's name.
 
 What to hold it against: one training step of the same batch (``bench.py --train``, measured in the same session and handed in
 with --train-step-ms): a batch made on RoomSimulator's side stream hides behind a step when "all" is below it.
@@ -54,12 +56,12 @@ def events(fn, reps):
     return best
 
 
-def scenes_of(settings, rt60=None):
+def scenes_of(settings, rt60=None, method="ism"):
     st = copy.deepcopy(settings)
     st["noise"]["n"] = [NOISES, NOISES]
     if rt60 is not None:
         st["room"]["rt60"] = [rt60, rt60]
-    return [sim.sample_scene(st, np.random.default_rng(1000 + b), rir_method="ism") for b in range(B)]
+    return [sim.sample_scene(st, np.random.default_rng(1000 + b), rir_method=method) for b in range(B)]
 
 
 def workload(name, scenes, x, dev, reps):
@@ -68,6 +70,7 @@ def workload(name, scenes, x, dev, reps):
     ks = sim.response_lengths(scenes)
     K = max(ks)
     lib = eabnet_amd._lib.load()
+    method = scenes[0].rir_method
     records = sim._to_device(np.stack([sim._scene_record(sc) for sc in scenes]), dev)
     lens = torch.full((B,), L, dtype=torch.int32, device=dev)
     klen = torch.tensor([[k, sim.first_arrival(sc)] for k, sc in zip(ks, scenes)], dtype=torch.int32, device=dev)
@@ -87,8 +90,11 @@ def workload(name, scenes, x, dev, reps):
     row = {"orders": [int(sc.max_order) for sc in scenes], "rt60": [round(float(sc.rt60), 3) for sc in scenes], "K": ks,
            "images_per_response": [(2 * o + 1) * (2 * o * o + 2 * o + 3) // 3 for o in (int(sc.max_order) for sc in scenes)],
            "workspace_MB": round(wb / 2 ** 20, 1), "responses_MB": round(h.numel() * 4 / 2 ** 20, 1)}
+    if method == "ism_tail":                                           # what the launch adds instead: images inside r_mix, and the tail's
+        row["tail_start"], row["tail_density"] = scenes[0].tail_start, scenes[0].tail_density
+        row["tail_images_per_response"] = [int(np.ceil(sc.tail_density * max(0, k - sim.TAPS - int(sc.tail_start * sc.fs)))) for sc, k in zip(scenes, ks)]
     row["gains_ms"] = round(events(lambda: sim._launch_gains(x, lens, records, fs, partial, nwin, gains), reps), 3)
-    row["rirs_ms"] = round(events(lambda: sim._launch_rirs(records, B, S, M, K, fs, h), reps), 3)
+    row["rirs_ms"] = round(events(lambda: sim._launch_rirs(records, B, S, M, K, fs, h, method), reps), 3)
     row["convolve_ms"] = round(events(conv, reps), 3)
     row["all_ms"] = round(events(lambda: sim.simulate_rooms(x, scenes), reps), 3)
     print(name, row, flush=True)
@@ -113,6 +119,7 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--train-step-ms", type=float, default=None, help="one training step of the same batch (bench.py --train)")
+    ap.add_argument("--method", choices=["ism", "ism_tail", "both"], default="ism", help="the response model of the scenes")
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--host-only", action="store_true", help="only the host stand-in (needs no GPU); merged into --out when it exists")
     ap.add_argument("--out", default=None)
@@ -132,13 +139,16 @@ def main() -> None:
     x = x.to(dev)
     res = {"workload": {"B": B, "seconds": SECONDS, "fs": FS, "mics": 8, "sources": 1 + NOISES}}
     draws = scenes_of(settings)
-    res["settings"] = workload("settings", draws, x, dev, args.reps)
-    res["worst"] = workload("worst", scenes_of(settings, 0.7), x, dev, max(1, args.reps // 2))
     if args.train_step_ms is not None:
         res["train_step_ms"] = args.train_step_ms
-        for k in ("settings", "worst"):
-            res[k]["hides_behind_a_step"] = bool(res[k]["all_ms"] < args.train_step_ms)
-            res[k]["bound_by"] = max(("gains_ms", "rirs_ms", "convolve_ms"), key=lambda n: res[k][n])
+    for method in (["ism", "ism_tail"] if args.method == "both" else [args.method]):
+        rows = res.setdefault(method, {}) if args.method == "both" else res
+        rows["settings"] = workload(f"{method} settings", scenes_of(settings, method=method), x, dev, args.reps)
+        rows["worst"] = workload(f"{method} worst", scenes_of(settings, 0.7, method=method), x, dev, max(1, args.reps // 2))
+        if args.train_step_ms is not None:
+            for k in ("settings", "worst"):
+                rows[k]["hides_behind_a_step"] = bool(rows[k]["all_ms"] < args.train_step_ms)
+                rows[k]["bound_by"] = max(("gains_ms", "rirs_ms", "convolve_ms"), key=lambda n: rows[k][n])
     if not args.no_host:
         res["host_stand_in"] = host_stand_in(draws[0], x[0].cpu().numpy().astype(np.float64))
         print("host", res["host_stand_in"], flush=True)
