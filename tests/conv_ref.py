@@ -2,7 +2,8 @@
 output element  (TEST INFRASTRUCTURE).
 
 conv_ref(op, arena) evaluates the formula documented above eab_conv_desc in float64 from the fp32 arrays the op names and
-returns, per output region (dst, dst_acc, f2_dst, the statistics partials, the fz_* tables and the arrival counter), the
+returns, per output region (dst, dst_acc, f2_dst, the GLU factor dump of the training programs, the statistics partials, the
+fz_* tables and the arrival counter), the
 value, a limit on the error of a correct fp32 evaluation of it, and the set of elements the launch writes.  The weights are
 unpacked with the project's own helpers (prg.unpack_frag, prg.glu_row_order, the emulator's unit order and unpack_f16x3).
 
@@ -99,8 +100,10 @@ def regions(op: prg.ConvOp) -> List[Tuple[str, prg.Ref, tuple, bool, str]]:
            ("f2_w", op.f2_w, (op.f2_N * N,), False, "r"), ("f2_dst", op.f2_dst, (B, T, 1, op.f2_N), True, "w"),
            ("f2_stats", op.f2_stats, (B, op.f2_stat_tiles, op.f2_nsets, op.f2_N, 4), True, "w"),
            ("f2_stat_slope0", op.f2_stat_slope0, (op.f2_N,), False, "r"),
-           ("f2_stat_slope1", op.f2_stat_slope1, (op.f2_N,), False, "r")]
-    assert op.glu_dump is None and not op.src_bf16, "training-only fields are not part of this reference"
+           ("f2_stat_slope1", op.f2_stat_slope1, (op.f2_N,), False, "r"),
+           ("glu_dump", op.glu_dump, (B, T, op.Fout, N), True, "w")]
+    assert not op.src_bf16, "bf16-stored sources (bf16 training programs) are not part of this reference"
+    assert op.glu_dump is None or op.epi == prg.EPI_GLU, "only the GLU epilogue dumps its factors"
     return [r for r in out if r[1] is not None]
 
 
@@ -373,6 +376,16 @@ class _Launch:
             sg = _sig(g)
             out = a * sg
             lo = sg * la + np.abs(a) * sg * (1 - sg) * lg + 0.25 * la * lg + np.abs(out) * ((np.abs(g) + 6) * 2.0 ** -23 + 2 * U)
+            if op.glu_dump is not None:
+                # training: the two factors of every row this launch produces, [B][T][Fout][N] in the packed column order --
+                # value columns acc + bias (the accumulator's own limit), gate columns sigmoid(acc + bias) (sigmoid' <= 1/4,
+                # |sigmoid''| < 0.1, and the epilogue's allowance for the device's exp and reciprocal)
+                dump = self.out("glu_dump", op.glu_dump, (B, T, Fout, N))
+                dv, dl = np.empty(acc.shape), np.empty(acc.shape)
+                dv[..., rv], dl[..., rv] = a, la
+                dv[..., rv + 32] = sg
+                dl[..., rv + 32] = sg * (1 - sg) * lg + 0.1 * lg * lg + sg * ((np.abs(g) + 6) * 2.0 ** -23 + 2 * U)
+                put(dump, np.arange(No) * op.ostride + ophase, dv, dl)
         else:
             out, lo = acc, lim
         assert out.shape[-1] == Cout

@@ -1,7 +1,10 @@
 """Kernel-level parity of the training kernels (csrc/train.hip, wgrad.hip, lstm_bwd.hip) on a real MI355X, through
 the C ABI, each against fp64 PyTorch autograd of the reference layer it differentiates (the layers the reference's
 loss.backward() walks through: train_distributed.py:228 over EaBNet.py).  Tolerance 1e-5 relative (max-abs/max and
-L2): these are single kernels on well-conditioned random data, so they sit at the fp32 rounding floor."""
+L2): these are single kernels on well-conditioned random data, so they sit at the fp32 rounding floor.
+The kernels no call here reaches (the cLN backward, the multi-view norm pair, eab_in_finalize_mr_f32, eab_glu_bwd_ex_f32,
+eab_wgrad_batch_f32, eab_gather_f32, eab_gag_crm_bwd_f32, the GLU factor dump, the dgrad launches) and the in-place call
+forms of the lowering are checked by the lockstep walk of the training programs, tests/test_train_walk_gpu.py."""
 import ctypes as C
 
 import numpy as np
