@@ -13,7 +13,7 @@
 // eab_com_mag_mse_loss_lens_f32: the masked loss of loss.hip for every utterance alone; its valid bins are the first
 // frames[b]*F floats of each of its two planes, i.e. two contiguous rows per spectrum.
 //
-// Determinism (both): the sample (bin) index is cut into SPANS of SCORE_SPAN = 4096, workgroup (span, b) owns span `span` of
+// Determinism (both): the sample (bin) index is cut into SPANS of EAB_SPAN = 4096 (rows.h), workgroup (span, b) owns span `span` of
 // utterance b whatever B, the row length, the row's alignment and the neighbours are.  Inside a span lane `tid` owns the indices
 // j*1024 + 4*tid + {0..3}, j = 0..3, and adds them in that order; a row whose address is 16-byte aligned loads its four as one
 // dwordx4, any other row (and the quad that straddles the row's length) loads them one by one AT THE SAME indices, so the bits do
@@ -22,44 +22,22 @@
 // Bound: launch latency and HBM (3 * L * 4 bytes per utterance; 4 * frames * F * 4 bytes for the loss).
 #include "rows.h"
 
-#define SCORE_THREADS 256
-#define SCORE_SPAN 4096                       /* samples per workgroup: 4 rounds of 256 lanes x 4 samples */
-
-// acc[0..NQ) of all 256 lanes -> dst[0..NQ): shuffle tree in the wave, waves 0..3 in order
-template <int NQ>
-__device__ __forceinline__ void score_reduce(double acc[NQ], double* __restrict__ dst) {
-    __shared__ double red[SCORE_THREADS / 64][NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; ++q)
-        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int q = 0; q < NQ; ++q) red[wave][q] = acc[q];
-    __syncthreads();
-    if (threadIdx.x < NQ) {
-        double s = red[0][threadIdx.x];
-        for (int w = 1; w < SCORE_THREADS / 64; ++w) s += red[w][threadIdx.x];
-        dst[threadIdx.x] = s;
-    }
-}
-
 typedef EabRows<3> ScoreRows;       // estimate, clean, noisy
 
-__global__ __launch_bounds__(SCORE_THREADS) void energy_partial_kernel(const ScoreRows rows, const int32_t* __restrict__ lens,
+__global__ __launch_bounds__(EAB_SPAN_THREADS) void energy_partial_kernel(const ScoreRows rows, const int32_t* __restrict__ lens,
                                                                        int spans, double* __restrict__ partial) {
     const int b = blockIdx.y, span = blockIdx.x;
-    const int le = eab_clamp(lens[3 * b], rows.cap[0]), ls = eab_clamp(lens[3 * b + 1], rows.cap[1]),
-              ly = eab_clamp(lens[3 * b + 2], rows.cap[2]);
+    const int le = eab_len(lens, rows, b, 0), ls = eab_len(lens, rows, b, 1), ly = eab_len(lens, rows, b, 2);
     const int longest = max(le, max(ls, ly));
-    if ((long long)span * SCORE_SPAN >= longest) return;          // (workgroup-uniform) the final kernel does not read this row
+    if ((long long)span * EAB_SPAN >= longest) return;          // (workgroup-uniform) the final kernel does not read this row
     const float* e = rows.p[0] + (long long)b * rows.stride[0];
     const float* s = rows.p[1] + (long long)b * rows.stride[1];
     const float* y = rows.p[2] + (long long)b * rows.stride[2];
     const bool ae = eab_aligned16(e), as = eab_aligned16(s), ay = eab_aligned16(y);
     double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-    for (int j = 0; j < SCORE_SPAN / (4 * SCORE_THREADS); ++j) {
-        const int i = span * SCORE_SPAN + j * 4 * SCORE_THREADS + 4 * (int)threadIdx.x;
+    for (int j = 0; j < EAB_SPAN / (4 * EAB_SPAN_THREADS); ++j) {
+        const int i = eab_span_quad(span, j, (int)threadIdx.x);
         if (i < longest) {
             float ve[4], vs[4], vy[4];
             eab_load4(e, ae, i, le, ve);
@@ -77,17 +55,16 @@ __global__ __launch_bounds__(SCORE_THREADS) void energy_partial_kernel(const Sco
             }
         }
     }
-    score_reduce<6>(acc, partial + ((long long)b * spans + span) * 6);
+    eab_span_reduce<6>(acc, partial + ((long long)b * spans + span) * 6);
 }
 
 __global__ void energy_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ lens, const ScoreRows rows,
                                     int B, int spans, double* __restrict__ out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int le = eab_clamp(lens[3 * b], rows.cap[0]), ls = eab_clamp(lens[3 * b + 1], rows.cap[1]),
-              ly = eab_clamp(lens[3 * b + 2], rows.cap[2]);
+    const int le = eab_len(lens, rows, b, 0), ls = eab_len(lens, rows, b, 1), ly = eab_len(lens, rows, b, 2);
     const int longest = max(le, max(ls, ly));
-    const int used = (int)(((long long)longest + SCORE_SPAN - 1) / SCORE_SPAN);
+    const int used = (int)(((long long)longest + EAB_SPAN - 1) / EAB_SPAN);
     double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = 0; k < used; ++k)
         for (int q = 0; q < 6; ++q) a[q] += partial[((long long)b * spans + k) * 6 + q];
@@ -114,11 +91,9 @@ extern "C" int eab_energy_ratios_f32(const float* est, long long est_stride, int
                                      eab_stream_t stream) {
     const ScoreRows rows = {{est, clean, noisy}, {est_stride, clean_stride, noisy_stride}, {est_cap, clean_cap, noisy_cap}};
     EAB_CHECK_ARG(lens && partial && out && eab_rows_ok(rows, B));
-    int cap = est_cap > clean_cap ? est_cap : clean_cap;
-    cap = cap > noisy_cap ? cap : noisy_cap;
-    const int spans = (cap + SCORE_SPAN - 1) / SCORE_SPAN;
+    const int spans = eab_rows_spans(rows);
     EAB_CHECK_ARG(partial_spans >= spans);
-    hipLaunchKernelGGL(energy_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(SCORE_THREADS), 0, eab_stream(stream), rows,
+    hipLaunchKernelGGL(energy_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(EAB_SPAN_THREADS), 0, eab_stream(stream), rows,
                        lens, partial_spans, partial);
     hipLaunchKernelGGL(energy_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, eab_stream(stream), partial, lens, rows, B,
                        partial_spans, out);
@@ -127,12 +102,12 @@ extern "C" int eab_energy_ratios_f32(const float* est, long long est_stride, int
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // per-utterance loss: esti [B][2][T_esti][F], label [B][2][T_label][F]; the valid bins of utterance b are i < frames[b]*F of a plane
-__global__ __launch_bounds__(SCORE_THREADS) void loss_lens_partial_kernel(const float* __restrict__ esti, const float* __restrict__ label,
+__global__ __launch_bounds__(EAB_SPAN_THREADS) void loss_lens_partial_kernel(const float* __restrict__ esti, const float* __restrict__ label,
                                                                           const int32_t* __restrict__ frames, int T_esti, int T_label,
                                                                           int T_max, int F, int spans, double* __restrict__ partial) {
     const int b = blockIdx.y, span = blockIdx.x;
     const int len = eab_clamp(frames[b], T_max) * F;
-    if ((long long)span * SCORE_SPAN >= len) return;
+    if ((long long)span * EAB_SPAN >= len) return;
     const long long pe = (long long)T_esti * F, pl = (long long)T_label * F;
     const float* er = esti + (long long)b * 2 * pe;
     const float* lr = label + (long long)b * 2 * pl;
@@ -141,8 +116,8 @@ __global__ __launch_bounds__(SCORE_THREADS) void loss_lens_partial_kernel(const 
     const bool a0 = eab_aligned16(er), a1 = eab_aligned16(ei), a2 = eab_aligned16(lr), a3 = eab_aligned16(li);
     double acc[2] = {0.0, 0.0};
 #pragma unroll
-    for (int j = 0; j < SCORE_SPAN / (4 * SCORE_THREADS); ++j) {
-        const int i = span * SCORE_SPAN + j * 4 * SCORE_THREADS + 4 * (int)threadIdx.x;
+    for (int j = 0; j < EAB_SPAN / (4 * EAB_SPAN_THREADS); ++j) {
+        const int i = eab_span_quad(span, j, (int)threadIdx.x);
         if (i < len) {
             float v0[4], v1[4], v2[4], v3[4];
             eab_load4(er, a0, i, len, v0);
@@ -158,7 +133,7 @@ __global__ __launch_bounds__(SCORE_THREADS) void loss_lens_partial_kernel(const 
             }
         }
     }
-    score_reduce<2>(acc, partial + ((long long)b * spans + span) * 2);
+    eab_span_reduce<2>(acc, partial + ((long long)b * spans + span) * 2);
 }
 
 __global__ void loss_lens_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ frames, int B, int T_max, int F,
@@ -166,7 +141,7 @@ __global__ void loss_lens_final_kernel(const double* __restrict__ partial, const
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int len = eab_clamp(frames[b], T_max) * F;
-    const int used = (len + SCORE_SPAN - 1) / SCORE_SPAN;
+    const int used = (len + EAB_SPAN - 1) / EAB_SPAN;
     double a = 0.0, c = 0.0;
     for (int k = 0; k < used; ++k) {
         a += partial[((long long)b * spans + k) * 2];
@@ -181,9 +156,9 @@ extern "C" int eab_com_mag_mse_loss_lens_f32(const float* esti, const float* lab
     EAB_CHECK_ARG(esti && label && frames && partial && loss && B > 0 && B <= 65535 && T_esti > 0 && T_label > 0 && F > 0);
     const int T_max = T_esti < T_label ? T_esti : T_label;
     EAB_CHECK_ARG((long long)T_max * F <= EAB_ROWS_MAX_LEN);
-    const int spans = (T_max * F + SCORE_SPAN - 1) / SCORE_SPAN;
+    const int spans = eab_spans(T_max * F);
     EAB_CHECK_ARG(partial_spans >= spans);
-    hipLaunchKernelGGL(loss_lens_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(SCORE_THREADS), 0, eab_stream(stream), esti,
+    hipLaunchKernelGGL(loss_lens_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(EAB_SPAN_THREADS), 0, eab_stream(stream), esti,
                        label, frames, T_esti, T_label, T_max, F, partial_spans, partial);
     hipLaunchKernelGGL(loss_lens_final_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, eab_stream(stream), partial, frames, B,
                        T_max, F, partial_spans, loss);

@@ -84,14 +84,6 @@ __device__ __forceinline__ int mr_len(const int32_t* __restrict__ lens, int b, i
     return n < nmin ? nmin : (n > cap ? cap : n);
 }
 
-// reflect_pad(x, P)[i] as an index into the n samples (stft.hip); P < n: one reflection at most
-__device__ __forceinline__ int mr_reflect(int i, int P, int n) {
-    int j = i - P;
-    if (j < 0) j = -j;
-    if (j >= n) j = 2 * (n - 1) - j;
-    return j;
-}
-
 // bins k and NH - k of one real frame from its packed half-length transform (stft.hip): X[k] = E + W^k O, X[NH-k] = conj(E - W^k O)
 __device__ __forceinline__ void mr_split(const float2* __restrict__ z, const float2* __restrict__ tw, int NH, int k, float2 x[2]) {
     const float2 a = z[k], ac = z[k == 0 ? 0 : NH - k];
@@ -138,7 +130,7 @@ __global__ __launch_bounds__(MR_MAX_THREADS) void mrstft_frames_kernel(const MrR
 #pragma unroll
         for (int sig = 0; sig < FFT_SIGS; ++sig) {
             const int t = t0 + (sig & (MR_FRAMES - 1));
-            v[sig] = under && t < T ? (sig < MR_FRAMES ? pe : ps)[mr_reflect(t * hop + idx, NH, n)] : 0.0f;
+            v[sig] = under && t < T ? (sig < MR_FRAMES ? pe : ps)[eab_reflect(t * hop + idx, NH, n)] : 0.0f;
         }
 #pragma unroll
         for (int sig = 0; sig < FFT_SIGS; ++sig) fr[sig * N + idx] = w * v[sig];
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(MR_MAX_THREADS) void mrstft_frames_kernel(const MrR
         }
     }
     if (!BWD) {
-        // lanes by the fixed shuffle tree, waves in index order (wave_loss.hip)
+        // lanes by the fixed shuffle tree, waves in index order (as eab_span_reduce of rows.h, for nthr lanes)
 #pragma unroll
         for (int q = 0; q < 3; ++q)
             for (int o = 32; o > 0; o >>= 1) acc[q] += __shfl_down(acc[q], o, 64);

@@ -15,20 +15,12 @@
 // kernel does ~6.6 kFLOP per frame and mic and is bound by its HBM traffic
 // (5,120 B read + 20,608 B written per frame at M = 8).  Sizes that do not
 // factor into {5,4,2} fall back to a direct DFT kernel.
-#include "common.h"
+#include "rows.h"
 #include "fft_lds.h"
 
 #define STFT_MAX_NFFT 512
 #define STFT_THREADS 256
 #define STFT_MC 8  // mics per pass held in registers
-
-// reflect_pad(x, P)[i] for i in [0, L + 2P): index into the un-padded wave.
-__device__ __forceinline__ int reflect_index(int i, int P, int L) {
-    int j = i - P;
-    if (j < 0) j = -j;
-    if (j >= L) j = 2 * (L - 1) - j;
-    return j;
-}
 
 // Per-utterance sample counts (eab_stft_compress_lens_f32): utterance b is the first lens[b] samples of its rows, which stay
 // L (the capacity) apart.  The count is clamped to (n_fft/2, L], so the gather stays in bounds whatever the array holds.
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_dft_kernel(
             int mm = e / n_fft, n = e - mm * n_fft;        // consecutive threads -> consecutive samples
             float v = 0.0f;
             if (m0 + mm < M) {
-                int j = reflect_index(t * hop + n, n_fft / 2, Lb);
+                int j = eab_reflect(t * hop + n, n_fft / 2, Lb);
                 v = window[n] * wav[((size_t)b * M + m0 + mm) * L + j];
             }
             fr[n * STFT_MC + mm] = v;
@@ -197,7 +189,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_fft_kernel(
                 const int mm = e / n_fft, n = e - mm * n_fft;
                 float v = 0.0f;
                 if (m0 + mm < M) {
-                    const float x = wav[((size_t)b * M + m0 + mm) * L + reflect_index(t * hop + n, NH, Lb)];
+                    const float x = wav[((size_t)b * M + m0 + mm) * L + eab_reflect(t * hop + n, NH, Lb)];
                     v = DUMP ? x : window[n] * x;
                 }
                 reinterpret_cast<float*>(buf0)[mm * n_fft + n] = v;       // float index 2*(n/2) + (n&1) = n

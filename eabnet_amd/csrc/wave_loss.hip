@@ -6,49 +6,30 @@
 //     es = <e,s>   ss = <s,s>   ee = <e,e>   alpha = es / ss   tgt = es^2 / ss   res = ee - tgt
 //     loss_b = -k [ ln(tgt + eps) - ln(res + eps) ]
 //     d loss_b / d e_i = a_b e_i + c_b s_i,    a_b = 2 k / (res + eps),   c_b = -2 k alpha [ 1 / (tgt + eps) + 1 / (res + eps) ]
-// eab_si_sdr_loss_f32: the three sums by score.hip's scheme (fp64 products of the fp32 samples, fixed spans of 4096 samples,
-// lanes by a fixed shuffle tree, waves in order, spans in index order: the row of an utterance has the same bits alone and in any
-// batch, whatever the strides and alignments), then ONE workgroup turns them into (loss_b, a_b, c_b) and the batch's sum and mean.
+// eab_si_sdr_loss_f32: the three sums by score.hip's scheme, with the helpers of rows.h (fp64 products of the fp32 samples, fixed
+// spans of EAB_SPAN = 4096 samples, eab_span_reduce: lanes by a fixed shuffle tree, waves in order; spans in index order: the row of
+// an utterance has the same bits alone and in any batch, whatever the strides and alignments), then ONE workgroup turns them into
+// (loss_b, a_b, c_b) and the batch's sum and mean.
 // eab_si_sdr_loss_bwd_f32: grad[b][i] = g_b (a_b e_i + c_b s_i) for i < Le_b, exactly 0 from there to the row's end; g_b is read
 // from device memory (autograd's grad_output: nothing goes through the host).  Three launches for a loss and its gradient, no
 // atomics.  Bound: launch latency and HBM (2 reads of each signal, one write of the gradient).
 #include "rows.h"
 
-#define WAVE_THREADS 256
-#define WAVE_SPAN 4096                        /* = SCORE_SPAN of score.hip: 4 rounds of 256 lanes x 4 samples */
-
 typedef EabRows<2> WaveRows;        // estimate, clean
 
-// acc[0..3) of all 256 lanes -> dst[0..3): shuffle tree in the wave, waves 0..3 in order (score_reduce of score.hip)
-__device__ __forceinline__ void wave_reduce3(double acc[3], double* __restrict__ dst) {
-    __shared__ double red[WAVE_THREADS / 64][3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_down(acc[q], off, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int q = 0; q < 3; ++q) red[wave][q] = acc[q];
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double s = red[0][threadIdx.x];
-        for (int w = 1; w < WAVE_THREADS / 64; ++w) s += red[w][threadIdx.x];
-        dst[threadIdx.x] = s;
-    }
-}
-
-__global__ __launch_bounds__(WAVE_THREADS) void si_sdr_partial_kernel(const WaveRows rows, const int32_t* __restrict__ lens, int spans,
+__global__ __launch_bounds__(EAB_SPAN_THREADS) void si_sdr_partial_kernel(const WaveRows rows, const int32_t* __restrict__ lens, int spans,
                                                                       double* __restrict__ partial) {
     const int b = blockIdx.y, span = blockIdx.x;
-    const int le = eab_clamp(lens[2 * b], rows.cap[0]), ls = eab_clamp(lens[2 * b + 1], rows.cap[1]);
+    const int le = eab_len(lens, rows, b, 0), ls = eab_len(lens, rows, b, 1);
     const int longest = max(le, ls);
-    if ((long long)span * WAVE_SPAN >= longest) return;           // (workgroup-uniform) the final kernel does not read this row
+    if ((long long)span * EAB_SPAN >= longest) return;           // (workgroup-uniform) the final kernel does not read this row
     const float* e = rows.p[0] + (long long)b * rows.stride[0];
     const float* s = rows.p[1] + (long long)b * rows.stride[1];
     const bool ae = eab_aligned16(e), as = eab_aligned16(s);
     double acc[3] = {0.0, 0.0, 0.0};
 #pragma unroll
-    for (int j = 0; j < WAVE_SPAN / (4 * WAVE_THREADS); ++j) {
-        const int i = span * WAVE_SPAN + j * 4 * WAVE_THREADS + 4 * (int)threadIdx.x;
+    for (int j = 0; j < EAB_SPAN / (4 * EAB_SPAN_THREADS); ++j) {
+        const int i = eab_span_quad(span, j, (int)threadIdx.x);
         if (i < longest) {
             float ve[4], vs[4];
             eab_load4(e, ae, i, le, ve);
@@ -62,22 +43,22 @@ __global__ __launch_bounds__(WAVE_THREADS) void si_sdr_partial_kernel(const Wave
             }
         }
     }
-    wave_reduce3(acc, partial + ((long long)b * spans + span) * 3);
+    eab_span_reduce<3>(acc, partial + ((long long)b * spans + span) * 3);
 }
 
 // one workgroup: lane `tid` takes the utterances tid, tid + 256, ...; the batch's sum adds each lane's values in that order and
 // the 256 lanes in lane order
-__global__ __launch_bounds__(WAVE_THREADS) void si_sdr_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ lens,
+__global__ __launch_bounds__(EAB_SPAN_THREADS) void si_sdr_final_kernel(const double* __restrict__ partial, const int32_t* __restrict__ lens,
                                                                     const WaveRows rows, int B, int spans, double eps,
                                                                     double* __restrict__ out, float* __restrict__ loss,
                                                                     float* __restrict__ total) {
-    __shared__ double lane_sum[WAVE_THREADS];
+    __shared__ double lane_sum[EAB_SPAN_THREADS];
     const double K = 4.342944819032518;                           // 10 / ln 10
     double mine = 0.0;
-    for (int b = threadIdx.x; b < B; b += WAVE_THREADS) {
-        const int le = eab_clamp(lens[2 * b], rows.cap[0]), ls = eab_clamp(lens[2 * b + 1], rows.cap[1]);
+    for (int b = threadIdx.x; b < B; b += EAB_SPAN_THREADS) {
+        const int le = eab_len(lens, rows, b, 0), ls = eab_len(lens, rows, b, 1);
         const int longest = max(le, ls);
-        const int used = (int)(((long long)longest + WAVE_SPAN - 1) / WAVE_SPAN);
+        const int used = (int)(((long long)longest + EAB_SPAN - 1) / EAB_SPAN);
         double a[3] = {0.0, 0.0, 0.0};
         for (int k = 0; k < used; ++k)
             for (int q = 0; q < 3; ++q) a[q] += partial[((long long)b * spans + k) * 3 + q];
@@ -95,20 +76,20 @@ __global__ __launch_bounds__(WAVE_THREADS) void si_sdr_final_kernel(const double
     __syncthreads();
     if (threadIdx.x == 0) {
         double s = 0.0;
-        for (int l = 0; l < WAVE_THREADS; ++l) s += lane_sum[l];
+        for (int l = 0; l < EAB_SPAN_THREADS; ++l) s += lane_sum[l];
         total[0] = (float)s;
         total[1] = (float)(s / (double)B);
     }
 }
 
 // grad row b: cap[0] floats, `gstride` floats between two rows; workgroup (span, b) writes span `span` of it
-__global__ __launch_bounds__(WAVE_THREADS) void si_sdr_bwd_kernel(const WaveRows rows, const int32_t* __restrict__ lens,
+__global__ __launch_bounds__(EAB_SPAN_THREADS) void si_sdr_bwd_kernel(const WaveRows rows, const int32_t* __restrict__ lens,
                                                                   const double* __restrict__ coef, const float* __restrict__ gout,
                                                                   int gout_stride, double scale, float* __restrict__ grad,
                                                                   long long gstride) {
     const int b = blockIdx.y, span = blockIdx.x;
     const int cap = rows.cap[0];
-    const int le = eab_clamp(lens[2 * b], cap), ls = eab_clamp(lens[2 * b + 1], rows.cap[1]);
+    const int le = eab_len(lens, rows, b, 0), ls = eab_len(lens, rows, b, 1);
     const float* e = rows.p[0] + (long long)b * rows.stride[0];
     const float* s = rows.p[1] + (long long)b * rows.stride[1];
     float* g = grad + (long long)b * gstride;
@@ -116,8 +97,8 @@ __global__ __launch_bounds__(WAVE_THREADS) void si_sdr_bwd_kernel(const WaveRows
     const double w = (double)gout[(long long)b * gout_stride] * scale;
     const double ca = w * coef[3 * b + 1], cc = w * coef[3 * b + 2];
 #pragma unroll
-    for (int j = 0; j < WAVE_SPAN / (4 * WAVE_THREADS); ++j) {
-        const int i = span * WAVE_SPAN + j * 4 * WAVE_THREADS + 4 * (int)threadIdx.x;
+    for (int j = 0; j < EAB_SPAN / (4 * EAB_SPAN_THREADS); ++j) {
+        const int i = eab_span_quad(span, j, (int)threadIdx.x);
         if (i >= cap) continue;
         float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (i < le) {
@@ -144,12 +125,11 @@ extern "C" int eab_si_sdr_loss_f32(const float* est, long long est_stride, int e
     const WaveRows rows = {{est, clean}, {est_stride, clean_stride}, {est_cap, clean_cap}};
     EAB_CHECK_ARG(lens && partial && out && loss && total && eab_rows_ok(rows, B));
     EAB_CHECK_ARG(eps >= 0.0 && eps < 1e300);                     // (refuses NaN too)
-    const int cap = est_cap > clean_cap ? est_cap : clean_cap;
-    const int spans = (cap + WAVE_SPAN - 1) / WAVE_SPAN;
+    const int spans = eab_rows_spans(rows);
     EAB_CHECK_ARG(partial_spans >= spans);
-    hipLaunchKernelGGL(si_sdr_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(WAVE_THREADS), 0, eab_stream(stream), rows, lens,
+    hipLaunchKernelGGL(si_sdr_partial_kernel, dim3((unsigned)spans, (unsigned)B), dim3(EAB_SPAN_THREADS), 0, eab_stream(stream), rows, lens,
                        partial_spans, partial);
-    hipLaunchKernelGGL(si_sdr_final_kernel, dim3(1), dim3(WAVE_THREADS), 0, eab_stream(stream), partial, lens, rows, B, partial_spans,
+    hipLaunchKernelGGL(si_sdr_final_kernel, dim3(1), dim3(EAB_SPAN_THREADS), 0, eab_stream(stream), partial, lens, rows, B, partial_spans,
                        eps, out, loss, total);
     EAB_RETURN_LAUNCH_STATUS();
 }
@@ -160,8 +140,8 @@ extern "C" int eab_si_sdr_loss_bwd_f32(const float* est, long long est_stride, i
     const WaveRows rows = {{est, clean}, {est_stride, clean_stride}, {est_cap, clean_cap}};
     EAB_CHECK_ARG(lens && coef && grad_out && grad && eab_rows_ok(rows, B));
     EAB_CHECK_ARG(grad_out_stride >= 0 && (B == 1 || grad_stride >= est_cap));
-    const int spans = (est_cap + WAVE_SPAN - 1) / WAVE_SPAN;
-    hipLaunchKernelGGL(si_sdr_bwd_kernel, dim3((unsigned)spans, (unsigned)B), dim3(WAVE_THREADS), 0, eab_stream(stream), rows, lens, coef,
+    const int spans = eab_spans(est_cap);
+    hipLaunchKernelGGL(si_sdr_bwd_kernel, dim3((unsigned)spans, (unsigned)B), dim3(EAB_SPAN_THREADS), 0, eab_stream(stream), rows, lens, coef,
                        grad_out, grad_out_stride, scale, grad, grad_stride);
     EAB_RETURN_LAUNCH_STATUS();
 }

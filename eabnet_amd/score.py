@@ -11,57 +11,28 @@ closed-form metrics of cal_single_metrics), ``stoi`` the same with the host libr
 ``Scorer(..., intelligibility=True)`` adds them as two more columns."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib
+from . import _rows as _rw
 from . import model as _m
-from .enhance import MODEL_RATE, Batch, Enhancer, _rs
+from .enhance import MODEL_RATE, Batch, Enhancer
 
-SPAN = 4096                                   # SCORE_SPAN of csrc/score.hip: samples (bins) per partial row
 METRICS = ("si_sdr", "si_sir", "si_sar", "si_sdr_mix", "loss")
 INTELLIGIBILITY_METRICS = ("stoi", "estoi")
 STOI_RATE = 10000                             # the rate of the definition: other rates are resampled to it first
 
 
-def _spans(n: int) -> int:
-    return max(1, -(-int(n) // SPAN))
-
-
-def _rows(t: torch.Tensor, name: str) -> torch.Tensor:
+def _rows(t: torch.Tensor) -> torch.Tensor:
+    """a signal of the scores as fp32 rows the kernels read (the losses refuse other dtypes; the scores cast them)"""
     if not t.is_cuda:
         raise _lib.EabError("energy_ratios needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
     if t.dtype != torch.float32:
         t = t.to(torch.float32)
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()                    # rows are read in place when their samples are contiguous
-    return t
-
-
-def _check_lens(lengths, B: int, widths: Sequence[int], what: str) -> list:
-    """the checked sample counts of one signal per width (``what`` names them: "triple (est, clean, noisy)"), each a list or a
-    device tensor; None: the full rows"""
-    if lengths is None:
-        lengths = [[w] * B for w in widths]
-    lengths = list(lengths)
-    if len(lengths) != len(widths):
-        raise ValueError(f"lengths must be a {what} of (B,) counts, got {len(lengths)} members")
-    return [_m.check_lengths(l, B, w, lo=1, unit="the signal's row length", integral=True) for l, w in zip(lengths, widths)]
-
-
-def _lens(cols: list, B: int, device: torch.device) -> torch.Tensor:
-    """checked counts as the (B, len(cols)) int32 device array of the kernels"""
-    if not any(isinstance(c, torch.Tensor) for c in cols):
-        return _m._device_lengths([v for row in zip(*cols) for v in row], device).view(B, len(cols))
-    return torch.stack([_m._device_lengths(c, device) for c in cols], dim=1).contiguous()
-
-
-def _row_args(B: int, *tensors: torch.Tensor) -> list:
-    """(pointer, floats between two rows, floats of a row that may be read) of every row tensor: EabRows of csrc/rows.h"""
-    return [a for t in tensors for a in (t.data_ptr(), t.stride(0) if B > 1 else t.shape[1], t.shape[1])]
+    return _rw.in_place(t)
 
 
 def energy_ratios(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, lengths=None, energies: bool = False) -> torch.Tensor:
@@ -81,19 +52,19 @@ def energy_ratios(est: torch.Tensor, clean: torch.Tensor, noisy: torch.Tensor, l
     B = est.shape[0]
     if clean.shape[0] != B or noisy.shape[0] != B:
         raise ValueError(f"est, clean and noisy must hold the same number of rows, got {B}, {clean.shape[0]}, {noisy.shape[0]}")
-    cols = _check_lens(lengths, B, (est.shape[1], clean.shape[1], noisy.shape[1]), "triple (est, clean, noisy)")
-    est, clean, noisy = _rows(est, "est"), _rows(clean, "clean"), _rows(noisy, "noisy")
+    cols = _rw.check_lens(lengths, B, (est.shape[1], clean.shape[1], noisy.shape[1]), "triple (est, clean, noisy)")
+    est, clean, noisy = _rows(est), _rows(clean), _rows(noisy)
     if not (est.device == clean.device == noisy.device):
         raise ValueError("est, clean and noisy must be on one device")
     widths = (est.shape[1], clean.shape[1], noisy.shape[1])
     lib = _lib.load()
     with torch.cuda.device(est.device):
-        lens = _lens(cols, B, est.device)
-        spans = _spans(max(widths))
+        lens = _rw.device_lens(cols, B, est.device)
+        spans = _rw.spans(max(widths))
         partial = torch.empty((B, spans, 6), dtype=torch.float64, device=est.device)
         out = torch.empty((B, 8), dtype=torch.float64, device=est.device)
-        _lib.check(lib.eab_energy_ratios_f32(*_row_args(B, est, clean, noisy), lens.data_ptr(), B, partial.data_ptr(), spans, out.data_ptr(),
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_energy_ratios_f32")
+        _lib.check(lib.eab_energy_ratios_f32(*_rw.row_args(B, est, clean, noisy), lens.data_ptr(), B, partial.data_ptr(), spans, out.data_ptr(),
+                                             _rw.stream()), "eab_energy_ratios_f32")
     return out if energies else out[:, :4]
 
 
@@ -116,18 +87,18 @@ def com_mag_mse_loss_per_utterance(esti: torch.Tensor, label: torch.Tensor, fram
     lab = label.detach().to(device=e.device, dtype=torch.float32).contiguous()
     with torch.cuda.device(e.device):
         fr = _m._device_lengths(frames, e.device)
-        spans = _spans(min(Te, Tl) * F)
+        spans = _rw.spans(min(Te, Tl) * F)
         partial = torch.empty((B, spans, 2), dtype=torch.float64, device=e.device)
         out = torch.empty((B,), dtype=torch.float64, device=e.device)
         _lib.check(lib.eab_com_mag_mse_loss_lens_f32(e.data_ptr(), lab.data_ptr(), fr.data_ptr(), B, Te, Tl, F, partial.data_ptr(),
-                                                     spans, out.data_ptr(), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+                                                     spans, out.data_ptr(), _rw.stream()),
                    "eab_com_mag_mse_loss_lens_f32")
     return out
 
 
 def _stoi_rows(est: torch.Tensor, clean: torch.Tensor, cols: list, taps: bool):
     """the five launches of csrc/stoi.hip on 10 kHz rows: (B, 2) float64 [stoi, estoi] (and the taps)"""
-    est, clean = _rows(est, "est"), _rows(clean, "clean")
+    est, clean = _rows(est), _rows(clean)
     if est.device != clean.device:
         raise ValueError("est and clean must be on one device")
     B = est.shape[0]
@@ -137,7 +108,7 @@ def _stoi_rows(est: torch.Tensor, clean: torch.Tensor, cols: list, taps: bool):
     if FC < 0 or nbytes < 0:
         raise ValueError(f"intelligibility takes at most 65535 rows of at most 2^30 samples, got {B} rows of {cap}")
     with torch.cuda.device(est.device):
-        lens = _lens(cols, B, est.device)
+        lens = _rw.device_lens(cols, B, est.device)
         work = torch.empty((nbytes,), dtype=torch.uint8, device=est.device)
         out = torch.empty((B, 2), dtype=torch.float64, device=est.device)
         tap = None
@@ -146,8 +117,8 @@ def _stoi_rows(est: torch.Tensor, clean: torch.Tensor, cols: list, taps: bool):
                    "kept": torch.zeros((B, FC), dtype=torch.int32, device=est.device),
                    "tob": torch.zeros((B, 2, 15, FC), dtype=torch.float32, device=est.device)}
         ptrs = [tap[k].data_ptr() for k in ("K", "kept", "tob")] if taps else [None, None, None]
-        _lib.check(lib.eab_stoi_f32(*_row_args(B, est, clean), lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), *ptrs,
-                                    C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_stoi_f32")
+        _lib.check(lib.eab_stoi_f32(*_rw.row_args(B, est, clean), lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), *ptrs,
+                                    _rw.stream()), "eab_stoi_f32")
     return (out, tap) if taps else out
 
 
@@ -173,14 +144,11 @@ def intelligibility(est: torch.Tensor, clean: torch.Tensor, lengths=None, sample
     B = est.shape[0]
     if clean.shape[0] != B:
         raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
-    cols = _check_lens(lengths, B, (est.shape[1], clean.shape[1]), "pair (est, clean)")
-    o, n = _rs._ratio(sample_rate, STOI_RATE)
+    cols = _rw.check_lens(lengths, B, (est.shape[1], clean.shape[1]), "pair (est, clean)")
+    _rw.check_rate(sample_rate, STOI_RATE)
     if not (est.is_cuda and clean.is_cuda):
         raise _lib.EabError("intelligibility needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
-    if o != n:
-        est, clean = (_rs.resample(_rows(t, "sig"), sample_rate, STOI_RATE, lengths=c) for t, c in zip((est, clean), cols))
-        cols = [(c.to(torch.int64) * n + (o - 1)) // o if isinstance(c, torch.Tensor) else [-(-n * v // o) for v in c]
-                for c in cols]
+    (est, clean), cols = _rw.to_rate((est, clean), cols, sample_rate, STOI_RATE, prepare=_rows)
     return _stoi_rows(est, clean, cols, taps)
 
 

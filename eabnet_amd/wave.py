@@ -22,15 +22,11 @@ import math
 import torch
 
 from . import _lib
+from . import _rows as _rw
 from . import model as _m
-from .enhance import _rs
-from .score import STOI_RATE, _lens, _row_args, _spans
+from .score import STOI_RATE
 
 REDUCTIONS = ("mean", "sum", "none")
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 class _SiSdrLoss(torch.autograd.Function):
@@ -43,13 +39,13 @@ class _SiSdrLoss(torch.autograd.Function):
         B = est.shape[0]
         e, s = est.detach(), clean
         with torch.cuda.device(e.device):
-            spans = _spans(max(e.shape[1], s.shape[1]))
+            spans = _rw.spans(max(e.shape[1], s.shape[1]))
             partial = torch.empty((B, spans, 3), dtype=torch.float64, device=e.device)
             coef = torch.empty((B, 3), dtype=torch.float64, device=e.device)
             loss = torch.empty((B,), dtype=torch.float32, device=e.device)
             total = torch.empty((2,), dtype=torch.float32, device=e.device)
-            _lib.check(lib.eab_si_sdr_loss_f32(*_row_args(B, e, s), lens.data_ptr(), B, float(eps), partial.data_ptr(), spans,
-                                               coef.data_ptr(), loss.data_ptr(), total.data_ptr(), _stream()), "eab_si_sdr_loss_f32")
+            _lib.check(lib.eab_si_sdr_loss_f32(*_rw.row_args(B, e, s), lens.data_ptr(), B, float(eps), partial.data_ptr(), spans,
+                                               coef.data_ptr(), loss.data_ptr(), total.data_ptr(), _rw.stream()), "eab_si_sdr_loss_f32")
         ctx.save_for_backward(e, s, lens, coef)
         ctx.reduction = reduction
         return loss if reduction == "none" else total[0 if reduction == "sum" else 1]
@@ -59,26 +55,12 @@ class _SiSdrLoss(torch.autograd.Function):
         e, s, lens, coef = ctx.saved_tensors
         lib = _lib.load()
         B, L = e.shape
-        g = g.detach()
-        if g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        per_row = ctx.reduction == "none"
-        gstride = g.stride(0) if per_row and B > 1 else 0
-        if gstride < 0:
-            g, gstride = g.contiguous(), 1
+        g, gstride, scale = _rw.grad_row(g, B, ctx.reduction)
         grad = torch.empty((B, L), dtype=torch.float32, device=e.device)
         with torch.cuda.device(e.device):
-            _lib.check(lib.eab_si_sdr_loss_bwd_f32(*_row_args(B, e, s), lens.data_ptr(), B, coef.data_ptr(), g.data_ptr(), gstride,
-                                                   1.0 / B if ctx.reduction == "mean" else 1.0, grad.data_ptr(), L, _stream()),
-                       "eab_si_sdr_loss_bwd_f32")
+            _lib.check(lib.eab_si_sdr_loss_bwd_f32(*_rw.row_args(B, e, s), lens.data_ptr(), B, coef.data_ptr(), g.data_ptr(), gstride,
+                                                   scale, grad.data_ptr(), L, _rw.stream()), "eab_si_sdr_loss_bwd_f32")
         return grad, None, None, None, None
-
-
-def _rows_in_place(t: torch.Tensor) -> torch.Tensor:
-    """rows are read in place when their samples are contiguous and two rows do not overlap; anything else is packed"""
-    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
-        t = t.contiguous()
-    return t
 
 
 def si_sdr_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, eps: float = 0.0, reduction: str = "mean") -> torch.Tensor:
@@ -97,42 +79,11 @@ def si_sdr_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, eps: float
         raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
     if not (isinstance(eps, (int, float)) and 0.0 <= float(eps) < float("inf")):
         raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
-    if clean.ndim == 3 and clean.shape[1] == 1:
-        clean = clean[:, 0]
-    for name, t in (("est", est), ("clean", clean)):
-        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError(f"{name} must be a (B, L) tensor (clean may be (B, 1, L)), got {tuple(t.shape)}")
-    B = est.shape[0]
-    if clean.shape[0] != B:
-        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
-    if est.dtype != torch.float32 or clean.dtype != torch.float32:
-        raise TypeError(f"si_sdr_loss takes fp32 waves, got {est.dtype} and {clean.dtype} (there is no operator fallback)")
-    if clean.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("si_sdr_loss is differentiable with respect to est only: clean requires grad (detach it; "
-                                  "there is no operator fallback)")
-    widths = (est.shape[1], clean.shape[1])
-    if lengths is None:
-        cols = [[w] * B for w in widths]
-    else:
-        if isinstance(lengths, torch.Tensor):
-            pairs = lengths.ndim == 2
-            if pairs and tuple(lengths.shape) != (B, 2):
-                raise ValueError(f"lengths must have shape ({B},) or ({B}, 2), got {tuple(lengths.shape)}")
-            cols = [lengths[:, 0], lengths[:, 1]] if pairs else [lengths, lengths]
-        else:
-            rows = list(lengths)
-            pairs = len(rows) > 0 and all(isinstance(r, (list, tuple)) for r in rows)
-            if pairs and (len(rows) != B or any(len(r) != 2 for r in rows)):
-                raise ValueError(f"lengths must hold {B} counts or {B} (est, clean) pairs")
-            cols = [[r[0] for r in rows], [r[1] for r in rows]] if pairs else [rows, rows]
-        cols = [_m.check_lengths(c, B, w, lo=1, unit="the signal's row length", integral=True) for c, w in zip(cols, widths)]
-    if not (est.is_cuda and clean.is_cuda):
-        raise _lib.EabError("si_sdr_loss needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
-    if est.device != clean.device:
-        raise ValueError("est and clean must be on one device")
-    est_rows, clean_rows = _rows_in_place(est), _rows_in_place(clean.detach())
+    clean, B = _rw.check_waves("si_sdr_loss", est, clean)
+    cols = _rw.check_lens(lengths, B, (est.shape[1], clean.shape[1]))
+    est_rows, clean_rows = _rw.device_rows("si_sdr_loss", est, clean)
     with torch.cuda.device(est.device):
-        lens = _lens(cols, B, est.device)
+        lens = _rw.device_lens(cols, B, est.device)
     return _SiSdrLoss.apply(est_rows, clean_rows, lens, float(eps), reduction)
 
 
@@ -218,9 +169,9 @@ class _MrStftLoss(torch.autograd.Function):
             coef = torch.empty((B, R, 2), dtype=torch.float64, device=e.device)
             loss = torch.empty((B,), dtype=torch.float32, device=e.device)
             total = torch.empty((2,), dtype=torch.float32, device=e.device)
-            _lib.check(lib.eab_mrstft_loss_f32(*_row_args(B, e, s), lens.data_ptr(), B, res_host, R, tables.data_ptr(), factor_sc,
+            _lib.check(lib.eab_mrstft_loss_f32(*_rw.row_args(B, e, s), lens.data_ptr(), B, res_host, R, tables.data_ptr(), factor_sc,
                                                factor_mag, floor, work.data_ptr(), nbytes, coef.data_ptr(), loss.data_ptr(),
-                                               total.data_ptr(), _stream()), "eab_mrstft_loss_f32")
+                                               total.data_ptr(), _rw.stream()), "eab_mrstft_loss_f32")
         ctx.save_for_backward(e, s, lens, coef, tables)
         ctx.res, ctx.floor, ctx.reduction = res, floor, reduction
         return loss if reduction == "none" else total[0 if reduction == "sum" else 1]
@@ -232,20 +183,14 @@ class _MrStftLoss(torch.autograd.Function):
         B, L = e.shape
         res, R = ctx.res, len(ctx.res)
         res_host = (C.c_int32 * (3 * R))(*[v for r in res for v in r])
-        g = g.detach()
-        if g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        per_row = ctx.reduction == "none"
-        gstride = g.stride(0) if per_row and B > 1 else 0
-        if gstride < 0:
-            g, gstride = g.contiguous(), 1
+        g, gstride, scale = _rw.grad_row(g, B, ctx.reduction)
         with torch.cuda.device(e.device):
             nbytes = lib.eab_mrstft_workspace_bytes(res_host, R, B, min(L, s.shape[1]), 1)
             work = torch.empty((nbytes // 4,), dtype=torch.float32, device=e.device)
             grad = torch.empty((B, L), dtype=torch.float32, device=e.device)
-            _lib.check(lib.eab_mrstft_loss_bwd_f32(*_row_args(B, e, s), lens.data_ptr(), B, res_host, R, tables.data_ptr(), ctx.floor,
-                                                   coef.data_ptr(), g.data_ptr(), gstride, 1.0 / B if ctx.reduction == "mean" else 1.0,
-                                                   work.data_ptr(), nbytes, grad.data_ptr(), L, _stream()), "eab_mrstft_loss_bwd_f32")
+            _lib.check(lib.eab_mrstft_loss_bwd_f32(*_rw.row_args(B, e, s), lens.data_ptr(), B, res_host, R, tables.data_ptr(), ctx.floor,
+                                                   coef.data_ptr(), g.data_ptr(), gstride, scale, work.data_ptr(), nbytes, grad.data_ptr(), L,
+                                                   _rw.stream()), "eab_mrstft_loss_bwd_f32")
         return grad, None, None, None, None, None, None, None
 
 
@@ -274,29 +219,13 @@ def mr_stft_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, resolutio
         if not (isinstance(v, (int, float)) and 0.0 <= float(v) < float("inf")):
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
     res = check_resolutions(resolutions)
-    if clean.ndim == 3 and clean.shape[1] == 1:
-        clean = clean[:, 0]
-    for name, t in (("est", est), ("clean", clean)):
-        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError(f"{name} must be a (B, L) tensor (clean may be (B, 1, L)), got {tuple(t.shape)}")
-    B = est.shape[0]
-    if clean.shape[0] != B:
-        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
-    if est.dtype != torch.float32 or clean.dtype != torch.float32:
-        raise TypeError(f"mr_stft_loss takes fp32 waves, got {est.dtype} and {clean.dtype} (there is no operator fallback)")
-    if clean.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("mr_stft_loss is differentiable with respect to est only: clean requires grad (detach it; "
-                                  "there is no operator fallback)")
+    clean, B = _rw.check_waves("mr_stft_loss", est, clean)
     cap, nmin = min(est.shape[1], clean.shape[1]), max(r[0] for r in res) // 2 + 1
     if cap < nmin:
         raise ValueError(f"rows of {cap} samples are too short for reflect padding: more than {nmin - 1} (max n_fft / 2) are needed")
     lens = [cap] * B if lengths is None else _m.check_lengths(lengths, B, cap, lo=nmin, unit="max n_fft / 2 < samples <= min(Le, Ls)",
                                                               integral=True)
-    if not (est.is_cuda and clean.is_cuda):
-        raise _lib.EabError("mr_stft_loss needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
-    if est.device != clean.device:
-        raise ValueError("est and clean must be on one device")
-    est_rows, clean_rows = _rows_in_place(est), _rows_in_place(clean.detach())
+    est_rows, clean_rows = _rw.device_rows("mr_stft_loss", est, clean)
     with torch.cuda.device(est.device):
         lens = _m._device_lengths(lens, est.device)
     return _MrStftLoss.apply(est_rows, clean_rows, lens, res, float(factor_sc), float(factor_mag), float(floor), reduction)
@@ -319,8 +248,8 @@ class _StoiLoss(torch.autograd.Function):
         with torch.cuda.device(e.device):
             work = torch.empty((nbytes,), dtype=torch.uint8, device=e.device)
             out = torch.empty((B, 2), dtype=torch.float64, device=e.device)
-            _lib.check(lib.eab_stoi_f32(*_row_args(B, e, s), lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), None, None,
-                                        None, _stream()), "eab_stoi_f32")
+            _lib.check(lib.eab_stoi_f32(*_rw.row_args(B, e, s), lens.data_ptr(), B, work.data_ptr(), nbytes, out.data_ptr(), None, None,
+                                        None, _rw.stream()), "eab_stoi_f32")
             loss = -(factor_stoi * out[:, 0] + factor_estoi * out[:, 1])
             if reduction != "none":
                 loss = loss.sum()
@@ -338,21 +267,14 @@ class _StoiLoss(torch.autograd.Function):
         clean_cap, factor_stoi, factor_estoi, reduction = ctx.cfg
         lib = _lib.load()
         B, L = e.shape
-        g = g.detach()
-        if g.dtype != torch.float32:
-            g = g.to(torch.float32)
-        per_row = reduction == "none"
-        gstride = g.stride(0) if per_row and B > 1 else 0
-        if gstride < 0:
-            g, gstride = g.contiguous(), 1
+        g, gstride, scale = _rw.grad_row(g, B, reduction)
         with torch.cuda.device(e.device):
             nbytes = lib.eab_stoi_bwd_workspace_bytes(B, max(L, clean_cap))
             scratch = torch.empty((nbytes,), dtype=torch.uint8, device=e.device)
             grad = torch.empty((B, L), dtype=torch.float32, device=e.device)
             _lib.check(lib.eab_stoi_bwd_f32(e.data_ptr(), e.stride(0) if B > 1 else L, L, clean_cap, lens.data_ptr(), B, work.data_ptr(),
-                                            work.numel(), factor_stoi, factor_estoi, g.data_ptr(), gstride,
-                                            1.0 / B if reduction == "mean" else 1.0, scratch.data_ptr(), nbytes, grad.data_ptr(), L,
-                                            _stream()), "eab_stoi_bwd_f32")
+                                            work.numel(), factor_stoi, factor_estoi, g.data_ptr(), gstride, scale,
+                                            scratch.data_ptr(), nbytes, grad.data_ptr(), L, _rw.stream()), "eab_stoi_bwd_f32")
         return grad, None, None, None, None, None
 
 
@@ -384,45 +306,11 @@ def stoi_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, sample_rate:
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
     if float(factor_stoi) == 0.0 and float(factor_estoi) == 0.0:
         raise ValueError("factor_stoi and factor_estoi must not both be zero")
-    o, n = _rs._ratio(sample_rate, STOI_RATE)
-    if clean.ndim == 3 and clean.shape[1] == 1:
-        clean = clean[:, 0]
-    for name, t in (("est", est), ("clean", clean)):
-        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError(f"{name} must be a (B, L) tensor (clean may be (B, 1, L)), got {tuple(t.shape)}")
-    B = est.shape[0]
-    if clean.shape[0] != B:
-        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
-    if est.dtype != torch.float32 or clean.dtype != torch.float32:
-        raise TypeError(f"stoi_loss takes fp32 waves, got {est.dtype} and {clean.dtype} (there is no operator fallback)")
-    if clean.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("stoi_loss is differentiable with respect to est only: clean requires grad (detach it; "
-                                  "there is no operator fallback)")
-    widths = (est.shape[1], clean.shape[1])
-    if lengths is None:
-        cols = [[w] * B for w in widths]
-    else:
-        if isinstance(lengths, torch.Tensor):
-            pairs = lengths.ndim == 2
-            if pairs and tuple(lengths.shape) != (B, 2):
-                raise ValueError(f"lengths must have shape ({B},) or ({B}, 2), got {tuple(lengths.shape)}")
-            cols = [lengths[:, 0], lengths[:, 1]] if pairs else [lengths, lengths]
-        else:
-            rows = list(lengths)
-            pairs = len(rows) > 0 and all(isinstance(r, (list, tuple)) for r in rows)
-            if pairs and (len(rows) != B or any(len(r) != 2 for r in rows)):
-                raise ValueError(f"lengths must hold {B} counts or {B} (est, clean) pairs")
-            cols = [[r[0] for r in rows], [r[1] for r in rows]] if pairs else [rows, rows]
-        cols = [_m.check_lengths(c, B, w, lo=1, unit="the signal's row length", integral=True) for c, w in zip(cols, widths)]
-    if not (est.is_cuda and clean.is_cuda):
-        raise _lib.EabError("stoi_loss needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
-    if est.device != clean.device:
-        raise ValueError("est and clean must be on one device")
-    est_rows, clean_rows = _rows_in_place(est), _rows_in_place(clean.detach())
-    if o != n:                                # as intelligibility: each signal with its own length, then the lengths at 10 kHz
-        est_rows, clean_rows = (_rs.resample(t, sample_rate, STOI_RATE, lengths=c) for t, c in zip((est_rows, clean_rows), cols))
-        cols = [(c.to(torch.int64) * n + (o - 1)) // o if isinstance(c, torch.Tensor) else [-(-n * v // o) for v in c]
-                for c in cols]
+    _rw.check_rate(sample_rate, STOI_RATE)
+    clean, B = _rw.check_waves("stoi_loss", est, clean)
+    cols = _rw.check_lens(lengths, B, (est.shape[1], clean.shape[1]))
+    est_rows, clean_rows = _rw.device_rows("stoi_loss", est, clean)
+    (est_rows, clean_rows), cols = _rw.to_rate((est_rows, clean_rows), cols, sample_rate, STOI_RATE)
     with torch.cuda.device(est.device):
-        lens = _lens(cols, B, est.device)
+        lens = _rw.device_lens(cols, B, est.device)
     return _StoiLoss.apply(est_rows, clean_rows, lens, float(factor_stoi), float(factor_estoi), reduction)

@@ -16,7 +16,7 @@
 
 #include "eabnet_hip.h"
 
-#define SPAN 4096                                                     /* SCORE_SPAN of csrc/score.hip */
+#define SPAN 4096                                                     /* EAB_SPAN of csrc/rows.h */
 
 template <class T>
 static bool take(FILE* f, T* dst, size_t n) { return fread(dst, sizeof(T), n, f) == n; }

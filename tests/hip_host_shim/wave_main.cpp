@@ -22,7 +22,7 @@ alignas(16) float smem[(2 * 512 + 2 * 8 * 512 + 512 + 8 * 2 * 257)];   // the la
 #include <cstring>
 #include <vector>
 
-#define SPAN 4096                                                     /* WAVE_SPAN of csrc/wave_loss.hip */
+#define SPAN 4096                                                     /* EAB_SPAN of csrc/rows.h */
 
 template <class T>
 static bool take(FILE* f, T* dst, size_t n) { return fread(dst, sizeof(T), n, f) == n; }

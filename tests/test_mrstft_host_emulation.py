@@ -7,41 +7,24 @@ the same-bits contract.  No GPU needed; the compiler is the one that builds the 
 
 Bounds: those of tests/test_mrstft_gpu.py -- 1e-4 relative on a value, 1e-5 of max |ref| on a gradient at floor = 0.02 (no bin power
 within 1e-5 relative of the floor, asserted on the float64 reference)."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_emulation
 import mrstft_ref as M
 from util import TOL_HIP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "hip_host_shim")
 TOL_GRAD = 1e-5
 FLOOR = 0.02
 LENGTHS = [33, 129, 257]
 SEEDS = {33: 11, 129: 12, 257: 13}
 
 
-def _compiler():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ (the compiler of the ROCm installation that builds the library)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mrstft_emulation") / "mrstft_emulation")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "eabnet_amd", "csrc"),
-           os.path.join(SHIM, "shim.cpp"), os.path.join(SHIM, "mrstft_main.cpp"), "-o", exe, "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+    return host_emulation.build(tmp_path_factory, "mrstft")
 
 
 def _run(program, tmp_path, pairs, weights, unaligned, floor=FLOOR, cap=None, factors=(1.0, 1.0)):
@@ -60,9 +43,7 @@ def _run(program, tmp_path, pairs, weights, unaligned, floor=FLOOR, cap=None, fa
         f.write(np.asarray(lens, np.int32).tobytes())
         f.write(np.asarray(weights, np.float32).tobytes())
         f.write(rows.tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([program, src, dst, str(int(unaligned))], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    host_emulation.run(program, src, dst, str(int(unaligned)))
     raw = open(dst, "rb").read()
     coef = np.frombuffer(raw, np.float64, B * R * 2).reshape(B, R, 2)
     loss = np.frombuffer(raw, np.float32, B, 16 * B * R)

@@ -3,38 +3,20 @@
 same source the GPU runs, on arrays allocated at their exact size, checked for accesses past a segment, against the float64
 restatement (tests/optim_ref.py) within its bounds, and for the same-bits contract of the chunk sums.  No GPU needed; the compiler
 is the one that builds the library."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_emulation
 import optim_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "hip_host_shim")
 CHUNK = 4096
-
-
-def _compiler():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ (the compiler of the ROCm installation that builds the library)")
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("optim_emulation") / "optim_emulation")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"),
-           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "optim.hip"), os.path.join(SHIM, "shim.cpp"),
-           os.path.join(SHIM, "optim_main.cpp"), "-o", exe, "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+    return host_emulation.build(tmp_path_factory, "optim", "optim.hip")
 
 
 def _run(program, tmp_path, segs, t, lr, betas, eps, wd, max_norm, grad_offset=0):
@@ -48,9 +30,7 @@ def _run(program, tmp_path, segs, t, lr, betas, eps, wd, max_norm, grad_offset=0
         for s in segs:
             for a in s:
                 f.write(np.ascontiguousarray(a, np.float32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([program, src, dst, str(grad_offset)], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    host_emulation.run(program, src, dst, str(grad_offset))
     raw = open(dst, "rb").read()
     chunks = struct.unpack("q", raw[:8])[0]
     o = 8

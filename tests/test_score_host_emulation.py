@@ -5,42 +5,24 @@ allocated at their exact size), for reads past a signal's length (NaN there), ag
 same-bits contract.  No GPU needed; the compiler is the one that builds the library.
 
 Bounds: those of tests/test_score_gpu.py -- 4.34e-4 dB = 10 log10(1 + 1e-4) on a ratio, 1e-5 relative on a loss."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_emulation
 import score_ref as R
 from util import TOL_HIP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "hip_host_shim")
 TOL_DB = 10.0 * np.log10(1.0 + TOL_HIP)
 # odd length with a scalar tail; L % 4 = 3; three different lengths (zero extension); and one that crosses the 4096-sample span: its
 # row has two workgroups, the other rows' second workgroups return early
 PICK = (R.CASES[1], R.CASES[2], R.CASES[5], (4101, 4099, 4090, 920, 0.8, 0.2, 0.1))
 
 
-def _compiler():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ (the compiler of the ROCm installation that builds the library)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("score_emulation") / "score_emulation")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"),
-           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "score.hip"), os.path.join(SHIM, "shim.cpp"),
-           os.path.join(SHIM, "score_main.cpp"), "-o", exe, "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+    return host_emulation.build(tmp_path_factory, "score", "score.hip")
 
 
 def _run(program, tmp_path, cases, spectra=None, unaligned=False):
@@ -62,9 +44,7 @@ def _run(program, tmp_path, cases, spectra=None, unaligned=False):
             f.write(struct.pack(f"{len(frames)}i", *frames))
             f.write(esti.astype(np.float32).tobytes())
             f.write(label.astype(np.float32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([program, src, dst, str(int(unaligned))], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    host_emulation.run(program, src, dst, str(int(unaligned)))
     raw = open(dst, "rb").read()
     Bl = 0 if spectra is None else spectra[0].shape[0]
     return np.frombuffer(raw, np.float64, 8 * B).reshape(B, 8), np.frombuffer(raw, np.float64, Bl, 64 * B)

@@ -7,38 +7,20 @@ needed; the compiler is the one that builds the library.
 Bounds: the kept frames must be exact (integer logic, and tests/test_stoi_ref.py shows >= 0.05 dB of margin on every frame).  The
 band values come from fp32 frames and an fp32 512-point FFT: a few fp32 roundings (6e-8) relative to the largest band, bound 1e-6.
 The scores are fp64 functions of those, normalised to [-1, 1]: bound 1e-6."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_emulation
 import stoi_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "hip_host_shim")
 PICK = (2, 3, 4)                                         # no frame; one segment, est shorter; frames removed
-
-
-def _compiler():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ (the compiler of the ROCm installation that builds the library)")
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stoi_emulation") / "stoi_emulation")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"),
-           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "stoi.hip"), os.path.join(SHIM, "shim.cpp"),
-           os.path.join(SHIM, "stoi_main.cpp"), "-o", exe, "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+    return host_emulation.build(tmp_path_factory, "stoi", "stoi.hip")
 
 
 def _run(program, tmp_path, cases, unaligned=False, taps=True):
@@ -52,9 +34,7 @@ def _run(program, tmp_path, cases, unaligned=False, taps=True):
             f.write(est.tobytes())
         for clean, _ in cases:
             f.write(clean.tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([program, src, dst, str(int(unaligned)), str(int(taps))], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    host_emulation.run(program, src, dst, str(int(unaligned)), str(int(taps)))
     raw = open(dst, "rb").read()
     FC = struct.unpack("i", raw[:4])[0]
     o = 4

@@ -6,42 +6,23 @@ and for the same-bits contract.  No GPU needed.
 
 Measured here (fp32 frames, fp32 transforms both ways, fp32 stored band values, fp64 segment statistics): the gradient is
 1.6e-7 to 5.1e-7 of max |ref| off float64 on every gradient case and factor setting -- the bar of the GPU tests, 1e-5, is asserted."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_emulation
 import stoi_loss_ref as G
 import stoi_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "hip_host_shim")
 BAR = 1e-5
 PICK = (2, 3, 4, -1)                                     # no frame (sentinel); one segment, est shorter; frames removed; est much shorter
 WEIGHTS = (1.0, 0.7, -1.3, 2.0)
 
 
-def _compiler():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ (the compiler of the ROCm installation that builds the library)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stoi_bwd_emulation") / "stoi_bwd_emulation")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"),
-           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "stoi.hip"), os.path.join(ROOT, "eabnet_amd", "csrc", "stoi_bwd.hip"),
-           os.path.join(SHIM, "shim.cpp"),
-           os.path.join(SHIM, "stoi_bwd_main.cpp"), "-o", exe, "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+    return host_emulation.build(tmp_path_factory, "stoi_bwd", "stoi.hip", "stoi_bwd.hip")
 
 
 def _run(program, tmp_path, cases, weights, factors, unaligned=False):
@@ -56,10 +37,7 @@ def _run(program, tmp_path, cases, weights, factors, unaligned=False):
             f.write(est.tobytes())
         for clean, _ in cases:
             f.write(clean.tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([program, src, dst, str(int(unaligned)), repr(factors[0]), repr(factors[1])], capture_output=True, text=True,
-                       env=env, timeout=900)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    host_emulation.run(program, src, dst, str(int(unaligned)), repr(factors[0]), repr(factors[1]), timeout=900)
     raw = open(dst, "rb").read()
     cap = struct.unpack("i", raw[:4])[0]
     out = np.frombuffer(raw, np.float64, 2 * B, 4).reshape(B, 2)

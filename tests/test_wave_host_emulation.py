@@ -5,19 +5,15 @@ arrays are allocated at their exact sizes), for reads past a length (NaN there),
 tests/wave_ref.py, and for the same-bits contract.  No GPU needed; the compiler is the one that builds the library.
 
 Bounds: those of tests/test_wave_loss_gpu.py -- 4.34e-4 dB = 10 log10(1 + 1e-4) on a value, 1e-5 of max |ref| on a gradient."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_emulation
 import wave_ref as W
 from util import TOL_HIP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "hip_host_shim")
 TOL_DB = 10.0 * np.log10(1.0 + TOL_HIP)
 TOL_GRAD = 1e-5
 # (est, clean) samples: one sample; one below, on and one above the 4096-sample span; two spans and a scalar tail -- shorter and
@@ -26,29 +22,13 @@ LENGTHS = [(1, 300), (4095, 4097), (4096, 4096), (4097, 4095), (2 * 4096 + 3, 50
 EPS = 1e-8
 
 
-def _compiler():
-    for c in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin", "clang++"), shutil.which("clang++")):
-        if c and os.path.exists(c):
-            return c
-    raise AssertionError("no clang++ (the compiler of the ROCm installation that builds the library)")
-
-
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("wave_emulation") / "wave_emulation")
-    cmd = [_compiler(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-ffp-contract=off", "-I", SHIM, "-I", os.path.join(ROOT, "include"),
-           "-x", "c++", os.path.join(ROOT, "eabnet_amd", "csrc", "wave_loss.hip"), os.path.join(SHIM, "shim.cpp"),
-           os.path.join(SHIM, "wave_main.cpp"), "-o", exe, "-lpthread"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return exe
+    return host_emulation.build(tmp_path_factory, "wave", "wave_loss.hip")
 
 
 def _child(program, mode, src, dst, flag):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0")
-    r = subprocess.run([program, mode, src, dst, str(int(flag))], capture_output=True, text=True, env=env, timeout=600)
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-4000:])
+    host_emulation.run(program, mode, src, dst, str(int(flag)))
     return open(dst, "rb").read()
 
 
