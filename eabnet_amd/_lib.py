@@ -187,6 +187,20 @@ _SIGS = {
     "eab_wgrad_f32": (C.c_int, [C.POINTER(WgradDesc), C.c_void_p]),
     "eab_wgrad_batchable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "eab_wgrad_batch_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    # training with per-utterance lengths (lens: device int32 [B])
+    "eab_lstm64_bwd_form": (C.c_int, [C.c_int] * 4),
+    "eab_train_in_stats_lens_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 4
+                                    + [C.c_void_p, C.c_int, C.c_void_p]),
+    "eab_train_in1d_lens_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 3 + [C.c_float] + [C.c_void_p] * 5
+                                + [C.c_void_p, C.c_int, C.c_void_p]),
+    "eab_train_in1d_multi_lens_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 5
+                                      + [C.c_void_p, C.c_int, C.c_void_p]),
+    "eab_train_norm_bwd_lens_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "eab_train_norm_bwd_multi_lens_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "eab_layernorm64_bwd_lens_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "eab_lstm64_bwd_lens_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "eab_filter_sum_ld_lens_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "eab_wgrad_batch_lens_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "eab_cln_stats_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 3 + [TimeWindow, C.c_void_p]),
     "eab_cln_apply_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [TimeWindow, C.c_void_p]),
     "eab_cln_step_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_float, TimeWindow, C.c_void_p]),

@@ -115,7 +115,13 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     const int tile = (int)vblk - b * tiles_per_b;
     // per-utterance length (eab_time_window.lens): rows of the padding frames are neither computed nor counted in the
     // statistics partials (a tile wholly past the length writes an n = 0 partial and still arrives at fz_counter)
-    if (d.win.lens) t_hi = min(t_hi, d.win.lens[b]);
+    // The same length bounds the SOURCE rows a tap may gather (t_src): causal taps never reach it, the look-ahead taps of a data
+    // gradient (Geometry.adjoint, dt > 0) would read the stale padding rows of the gradient tensor
+    int t_src = d.T;
+    if (d.win.lens) {
+        t_src = min(t_src, d.win.lens[b]);
+        t_hi = min(t_hi, t_src);
+    }
     const int Q = t_hi * d.No;                      // first row NOT computed
     const int q0 = t_lo * d.No + tile * BM;
     const int n_blk = blockIdx.y * BN;
@@ -285,7 +291,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
                 p_ok[pp] = p_all[pp] = false;
                 p_tf[pp] = 0;
                 if (64 * pp < P) {
-                    p_ok[pp] = srow + 64 * pp < P && (unsigned)t_in < (unsigned)d.T && (unsigned)(f - halo_lo) < (unsigned)d.Fin;
+                    p_ok[pp] = srow + 64 * pp < P && (unsigned)t_in < (unsigned)t_src && (unsigned)(f - halo_lo) < (unsigned)d.Fin;
                     // every position of this wave's sixteen real: the fused transform needs no zero-select in this pass
                     if (XF != EAB_XF_NONE) p_all[pp] = __builtin_amdgcn_ballot_w64(p_ok[pp]) == __builtin_amdgcn_ballot_w64(true);
                     p_tf[pp] = tf;
@@ -540,7 +546,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int p = 0; p < MI; ++p) {
                     const int tt = a_t[p] + dt, fi = a_f0[p] + io;
-                    tap_ok[p] = a_ok[p] && tt >= 0 && tt < d.T && fi >= 0 && fi < d.Fin;
+                    tap_ok[p] = a_ok[p] && tt >= 0 && tt < t_src && fi >= 0 && fi < d.Fin;
                     const unsigned pos = (unsigned)(a_tf[p] + dt * d.Fin + io);
                     tap_b0[p] = (pos * (unsigned)d.C0 + (unsigned)(skq * (w0 ? 8 : 4))) * esz0;
                     tap_b1[p] = (pos * (unsigned)d.C1 + (unsigned)(skq * (w1 ? 8 : 4))) * esz1;
@@ -598,7 +604,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
                 for (int p = 0; p < MI; ++p) {
                     const int tt = a_t[p] + dt, fi = a_f0[p] + io;
-                    tap_ok[p] = a_ok[p] && tt >= 0 && tt < d.T && fi >= 0 && fi < d.Fin;
+                    tap_ok[p] = a_ok[p] && tt >= 0 && tt < t_src && fi >= 0 && fi < d.Fin;
                     const unsigned pos = (unsigned)(a_tf[p] + dt * d.Fin + io);
                     tap_b0[p] = pos * (unsigned)(d.C0 * 4);
                     tap_b1[p] = pos * (unsigned)(d.C1 * 4);

@@ -47,7 +47,9 @@
     const int Kpad = ph1 ? d.ph1_Kpad : d.Kpad;
     const float* wfrag = ph1 ? d.ph1_w : d.w;
     // per-utterance length (eab_time_window.lens): padding frames are neither computed nor counted in the partials
-    const int Q = (d.win.lens ? min(t_hi, d.win.lens[b]) : t_hi) * No;
+    // the same length bounds the source rows a tap may gather (t_src): a data gradient's look-ahead taps stay off the padding
+    const int t_src = d.win.lens ? min(d.T, d.win.lens[b]) : d.T;
+    const int Q = min(t_hi, t_src) * No;
     const int q0 = t_lo * No + tile * BM;
     const float inv_no = 1.0f / (float)No;
     // row stride of the A tiles in ELEMENTS (fp32, or bf16 in the BF form): 16 bytes of padding per row
@@ -152,7 +154,7 @@
 #pragma unroll
             for (int j = 0; j < NS; ++j) {
                 const int ti = rw.t[j] + tp.x, fi = rw.f[j] + tp.y;
-                const bool ok = live & rw.ok[j] & (ti >= 0) & (ti < d.T) & (fi >= 0) & (fi < d.Fin);
+                const bool ok = live & rw.ok[j] & (ti >= 0) & (ti < t_src) & (fi >= 0) & (fi < d.Fin);
                 const unsigned off = ok ? (unsigned)(((ti * d.Fin + fi) * Cs + c) * 4) : EAB_OOB;
                 bt.ok[tt * NS + j] = ok;
                 bt.v[tt * NS + j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));

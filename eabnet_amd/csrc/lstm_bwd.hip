@@ -34,7 +34,7 @@ __device__ __forceinline__ float lb_tanh(float x) { return fmaf(2.0f, __builtin_
 template <bool BF>
 __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ dh_out,
                                                          const float* __restrict__ wcat, float* __restrict__ dgates, int T, int F,
-                                                         int S) {
+                                                         int S, const int* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) float dg[2][LB_SEQ * LB_LD];
     __shared__ __attribute__((aligned(16))) char dgb[BF ? 2 : 1][BF ? LB_SEQ * LBB_ROW : 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,11 +62,15 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
     size_t goff[4];       // float offset of gates[sq][0][0][u]
     size_t hoff[4];       // float offset of dh_out[b][0][f][u]
     bool ok[4];
+    int nt[4];            // steps of the sequence's utterance (lens: steps t >= nt load zeros, as steps t < 0 do -- the carries
+                          // through the padding stay zero and its dgates are written as zeros; per sequence: a workgroup's
+                          // sequences may belong to two utterances)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int sq = s0 + 4 * lk + r;
         ok[r] = sq < S;
         const int b = ok[r] ? sq / F : 0, f = ok[r] ? sq - b * F : 0;
+        nt[r] = lens ? min(lens[b], T) : T;
         goff[r] = ((size_t)(ok[r] ? sq : 0) * T * 5) * LB_H + u;
         hoff[r] = (((size_t)b * T) * F + f) * LB_H + u;
     }
@@ -87,7 +91,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
     auto load = [&](int t, float (&q)[7][4]) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const bool v = ok[r] && t >= 0;
+            const bool v = ok[r] && t >= 0 && t < nt[r];
             const float* gp = gates + goff[r] + (size_t)(t >= 0 ? t : 0) * g_t;
             q[0][r] = v ? gp[0] : 0.f;
             q[1][r] = v ? gp[LB_H] : 0.f;
@@ -186,7 +190,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
 
 __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restrict__ gates, const float* __restrict__ dh_out,
                                                            const float* __restrict__ wcat, float* __restrict__ dgates, int T, int F,
-                                                           int S) {
+                                                           int S, const int* __restrict__ lens) {
     __shared__ __attribute__((aligned(16))) float dg[2][4 * LBQ_LD];
     __shared__ __attribute__((aligned(16))) float part[4][4][LB_H];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -194,6 +198,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restri
     const int sq = blockIdx.x * 4 + es;
     const bool ok = sq < S;
     const int b = ok ? sq / F : 0, f = ok ? sq - b * F : 0;
+    const int nt = lens ? min(lens[b], T) : T;                    // (per sequence: see lstm64_bwd_kernel)
     const size_t goff = ((size_t)(ok ? sq : 0) * T * 5) * LB_H + eu;
     const size_t hoff = (((size_t)b * T) * F + f) * LB_H + eu;
     const size_t g_t = (size_t)5 * LB_H, h_t = (size_t)F * LB_H;
@@ -215,7 +220,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restri
                                                                          (unsigned)((size_t)S * T * LB_H * 4), 0x00020000);
     const unsigned gb = (unsigned)(goff * 4), hb = (unsigned)(hoff * 4), g_tb = (unsigned)(g_t * 4), h_tb = (unsigned)(h_t * 4);
     auto load = [&](int t, float (&q)[7]) {
-        const bool v = ok && t >= 0;
+        const bool v = ok && t >= 0 && t < nt;
         const unsigned go_ = v ? gb + (unsigned)t * g_tb : EAB_OOB;
         auto ld = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off) {
             return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
@@ -288,26 +293,46 @@ extern "C" int eab_lstm64_bwd_f32(const float* gates, const float* dh_out, const
     return eab_lstm64_bwd_prec_f32(gates, dh_out, wcat, dgates, B, T, F, EAB_PREC_F32, stream);
 }
 
+// Which kernel a problem takes (host only, nothing is launched): EAB_LSTM_BWD_FORM_Q = the 4-sequence kernel, _16 / _16_BF16 =
+// the 16-sequence kernel with fp32 / bf16 recurrent products, < 0 = invalid arguments.
+extern "C" int eab_lstm64_bwd_form(int B, int T, int F, int precision) {
+    if (B <= 0 || T <= 0 || F <= 0 || (precision != EAB_PREC_F32 && precision != EAB_PREC_BF16)) return -1;
+    const long long S = (long long)B * F;
+    if (S * T * 5 * LB_H >= (1ll << 40)) return -1;
+    if (precision == EAB_PREC_BF16 && S > 2048) return EAB_LSTM_BWD_FORM_16_BF16;
+    // the 4-sequence kernel masks its loads with the offset EAB_OOB = 2^31 of a buffer descriptor over the whole gate tensor:
+    // that offset must lie OUTSIDE the buffer, so the tensor stays below 2^31 bytes (larger problems take the 16-sequence kernel)
+    if (S <= 2048 && S * T * 5 * LB_H * 4 < (1ll << 31)) return EAB_LSTM_BWD_FORM_Q;
+    return EAB_LSTM_BWD_FORM_16;
+}
+
 extern "C" int eab_lstm64_bwd_prec_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, int B, int T, int F,
                                        int precision, eab_stream_t stream) {
+    return eab_lstm64_bwd_lens_f32(gates, dh_out, wcat, dgates, nullptr, B, T, F, precision, stream);
+}
+
+extern "C" int eab_lstm64_bwd_lens_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, const int32_t* lens,
+                                       int B, int T, int F, int precision, eab_stream_t stream) {
     EAB_CHECK_ARG(gates && dh_out && wcat && dgates && B > 0 && T > 0 && F > 0);
     EAB_CHECK_ARG(precision == EAB_PREC_F32 || precision == EAB_PREC_BF16);
     const long long S = (long long)B * F;
     EAB_CHECK_ARG(S * T * 5 * LB_H < (1ll << 40));
+    const int form = eab_lstm64_bwd_form(B, T, F, precision);
     // bf16: a step of the 16-sequence form is 8 short MFMAs instead of 64 long ones (742 vs 1004 us per layer at 2576 sequences);
     // up to 2048 sequences the 4-sequence fp32 kernel below is faster than either (655 vs 926 us at 966: four times the
     // workgroups, a quarter of the elementwise chain per lane) and exact, so small batches take it in every mode
-    if (precision == EAB_PREC_BF16 && S > 2048) {
+    if (form == EAB_LSTM_BWD_FORM_16_BF16) {
         hipLaunchKernelGGL(lstm64_bwd_kernel<true>, dim3((unsigned)((S + LB_SEQ - 1) / LB_SEQ)), dim3(256), 0, eab_stream(stream), gates,
-                           dh_out, wcat, dgates, T, F, (int)S);
+                           dh_out, wcat, dgates, T, F, (int)S, lens);
         EAB_RETURN_LAUNCH_STATUS();
     }
-    if (S <= 2048 && S * T * 5 * LB_H * 4 < (1ll << 32)) {       // (32-bit byte offsets in the 4-sequence kernel's buffer descriptors)
+    if (form == EAB_LSTM_BWD_FORM_Q) {
         hipLaunchKernelGGL(lstm64_bwd_q_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, eab_stream(stream), gates, dh_out, wcat,
-                           dgates, T, F, (int)S);
+                           dgates, T, F, (int)S, lens);
         EAB_RETURN_LAUNCH_STATUS();
     }
     const int grid = (int)((S + LB_SEQ - 1) / LB_SEQ);
-    hipLaunchKernelGGL(lstm64_bwd_kernel<false>, dim3(grid), dim3(256), 0, eab_stream(stream), gates, dh_out, wcat, dgates, T, F, (int)S);
+    hipLaunchKernelGGL(lstm64_bwd_kernel<false>, dim3(grid), dim3(256), 0, eab_stream(stream), gates, dh_out, wcat, dgates, T, F, (int)S,
+                       lens);
     EAB_RETURN_LAUNCH_STATUS();
 }

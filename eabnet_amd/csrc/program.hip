@@ -156,26 +156,28 @@ extern "C" int eab_run_program(const eab_op* ops, int n_ops, eab_stream_t stream
             case EAB_OP_GATHER:
                 rc = eab_gather_f32(EAB_P(0), (const int32_t*)o.p[1], (const int32_t*)o.p[2], EAB_W(3), EAB_N64(0), stream);
                 break;
+            // (training ops under per-utterance lengths, o.win.lens: the frame count T of an op that carries none travels in
+            // a free slot -- IN_STATS i[4], NORM_BWD i[5], LN_BWD i[2..3] = B, T; lens == NULL is the plain entry point)
             case EAB_OP_IN_STATS:
                 rc = o.p[6] && o.i[3] > 0
-                         ? eab_train_in1d_multi_f32(EAB_P(0), EAB_P(1), o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], EAB_P(2), EAB_P(3),
-                                                    EAB_W(4), EAB_W(5), EAB_W(6), stream)
-                     : o.p[6] ? eab_train_in1d_f32(EAB_P(0), EAB_P(1), o.i[0], o.i[1], o.i[2], o.f[0], EAB_P(2), EAB_P(3), EAB_W(4),
-                                                 EAB_W(5), EAB_W(6), stream)
-                            : eab_train_in_stats_f32(EAB_P(0), EAB_P(1), o.i[0], o.i[1], o.i[2], o.f[0], EAB_P(2), EAB_P(3),
-                                                     EAB_W(4), EAB_W(5), stream);
+                         ? eab_train_in1d_multi_lens_f32(EAB_P(0), EAB_P(1), o.i[0], o.i[1], o.i[2], o.i[3], o.f[0], EAB_P(2), EAB_P(3),
+                                                         EAB_W(4), EAB_W(5), EAB_W(6), o.win.lens, o.i[4], stream)
+                     : o.p[6] ? eab_train_in1d_lens_f32(EAB_P(0), EAB_P(1), o.i[0], o.i[1], o.i[2], o.f[0], EAB_P(2), EAB_P(3), EAB_W(4),
+                                                      EAB_W(5), EAB_W(6), o.win.lens, o.i[4], stream)
+                            : eab_train_in_stats_lens_f32(EAB_P(0), EAB_P(1), o.i[0], o.i[1], o.i[2], o.f[0], EAB_P(2), EAB_P(3),
+                                                          EAB_W(4), EAB_W(5), o.win.lens, o.i[4], stream);
                 break;
             case EAB_OP_TR_NORM_ACT:
                 rc = eab_train_norm_act_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_P(3), EAB_W(4), o.i[0], o.i[1], o.i[2], o.i[3],
                                             stream);
                 break;
             case EAB_OP_NORM_BWD:
-                rc = o.i[4] > 0 ? eab_train_norm_bwd_multi_f32(EAB_P(0), EAB_P(4), EAB_P(1), EAB_P(2), EAB_P(3), EAB_P(5), EAB_W(6),
-                                                               EAB_P(7), EAB_W(8), EAB_W(9), EAB_W(10), EAB_W(11), o.i[0], o.i[1],
-                                                               o.i[4], stream)
-                                : eab_train_norm_bwd_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_P(3), EAB_P(4), EAB_P(5), EAB_W(6), EAB_P(7),
-                                                         EAB_W(8), EAB_W(9), EAB_W(10), EAB_W(11), o.i[0], o.i[1], o.i[2], o.i[3],
-                                                         stream);
+                rc = o.i[4] > 0 ? eab_train_norm_bwd_multi_lens_f32(EAB_P(0), EAB_P(4), EAB_P(1), EAB_P(2), EAB_P(3), EAB_P(5), EAB_W(6),
+                                                                    EAB_P(7), EAB_W(8), EAB_W(9), EAB_W(10), EAB_W(11), o.i[0], o.i[1],
+                                                                    o.i[4], o.win.lens, o.i[5], stream)
+                                : eab_train_norm_bwd_lens_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_P(3), EAB_P(4), EAB_P(5), EAB_W(6), EAB_P(7),
+                                                              EAB_W(8), EAB_W(9), EAB_W(10), EAB_W(11), o.i[0], o.i[1], o.i[2], o.i[3],
+                                                              o.win.lens, o.i[5], stream);
                 break;
             case EAB_OP_GLU_BWD:
                 rc = eab_glu_bwd_ex_f32(EAB_P(0), EAB_P(1), EAB_W(2), EAB_N64(0), o.i[2], o.i[3], stream);
@@ -196,7 +198,7 @@ extern "C" int eab_run_program(const eab_op* ops, int n_ops, eab_stream_t stream
                 rc = eab_colsum_f32(EAB_P(0), EAB_W(1), EAB_N64(0), o.i[2], stream);
                 break;
             case EAB_OP_FILTER_SUM:
-                rc = eab_filter_sum_ld_f32(EAB_P(0), EAB_P(1), EAB_W(2), o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], stream);
+                rc = eab_filter_sum_ld_lens_f32(EAB_P(0), EAB_P(1), EAB_W(2), o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.win.lens, stream);
                 break;
             case EAB_OP_FS_BWD:
                 rc = eab_filter_sum_bwd_f32(EAB_P(0), EAB_P(1), EAB_W(2), o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], stream);
@@ -205,14 +207,14 @@ extern "C" int eab_run_program(const eab_op* ops, int n_ops, eab_stream_t stream
                 rc = eab_layernorm64_fwd_f32(EAB_P(0), EAB_P(1), EAB_P(2), o.f[0], EAB_W(3), EAB_W(4), EAB_N64(0), stream);
                 break;
             case EAB_OP_LN_BWD:
-                rc = eab_layernorm64_bwd_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_P(3), EAB_W(4), EAB_W(5), EAB_W(6), EAB_N64(0),
-                                             stream);
+                rc = eab_layernorm64_bwd_lens_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_P(3), EAB_W(4), EAB_W(5), EAB_W(6), EAB_N64(0),
+                                                  o.win.lens, o.i[2], o.i[3], stream);
                 break;
             case EAB_OP_LSTM_TRAIN:
                 rc = eab_lstm64_train_fwd_prec_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_W(3), EAB_W(4), o.i[0], o.i[1], o.i[2], o.i[3], stream);
                 break;
             case EAB_OP_LSTM_BWD:
-                rc = eab_lstm64_bwd_prec_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_W(3), o.i[0], o.i[1], o.i[2], o.i[3], stream);
+                rc = eab_lstm64_bwd_lens_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_W(3), o.win.lens, o.i[0], o.i[1], o.i[2], o.i[3], stream);
                 break;
             case EAB_OP_GAG_CRM_BWD:
                 rc = eab_gag_crm_bwd_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_P(3), EAB_P(4), EAB_W(5), EAB_W(6), EAB_W(7), EAB_W(8), o.i[0],
@@ -223,7 +225,7 @@ extern "C" int eab_run_program(const eab_op* ops, int n_ops, eab_stream_t stream
                 int run = 1;
                 while (k + run < n_ops && ops[k + run].kind == EAB_OP_WGRAD) ++run;
                 const int nb = eab_wgrad_batchable(&o.wgrad, run, (int)sizeof(eab_op));
-                rc = eab_wgrad_batch_f32(&o.wgrad, nb, (int)sizeof(eab_op), stream);
+                rc = eab_wgrad_batch_lens_f32(&o.wgrad, nb, (int)sizeof(eab_op), o.win.lens, stream);
                 k += nb - 1;
                 break;
             }

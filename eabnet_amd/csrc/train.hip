@@ -53,7 +53,11 @@ template <bool APPLY, int NPL>
 __global__ __launch_bounds__(16 * NPL) void in_stats_kernel(const float* __restrict__ x, const float* __restrict__ slope,
                                                               int P, int C, float eps, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float* __restrict__ xf,
-                                                              float* __restrict__ mr, float* __restrict__ y, int xC) {
+                                                              float* __restrict__ mr, float* __restrict__ y, int xC,
+                                                              const int* __restrict__ lens, int T) {
+    // per-utterance lengths (lens, T frames of P / T positions each): the statistics are those of the first Pn positions, the
+    // rows behind them are neither read nor written; P stays the row stride of a batch element.  lens == NULL: Pn = P.
+    const int Pn = lens ? min(lens[blockIdx.x], T) * (P / T) : P;
     // thread -> 4 channels (float4) x every 16th position; shifted sums (shift = the channel's first value, so a
     // nearly constant channel loses nothing to cancellation) in fp64, combined through LDS in a fixed order
     __shared__ double red[2][NPL][64];                  // NPL position lanes x 16 float4 channel groups (NPL = 64: 1024 threads,
@@ -73,16 +77,16 @@ __global__ __launch_bounds__(16 * NPL) void in_stats_kernel(const float* __restr
         for (int j = 0; j < 4; ++j) k[j] = eab_prelu(k[j], a[j]);
         // four rows in flight per thread: a workgroup owns its slab alone, so its own loads are all the memory-level
         // parallelism there is (one row per iteration ran at one memory latency per 16 rows)
-        for (int i0 = pl; i0 < P; i0 += 4 * NPL) {
+        for (int i0 = pl; i0 < Pn; i0 += 4 * NPL) {
             f32x4 v[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = i0 + NPL * u;
-                v[u] = i < P ? *reinterpret_cast<const f32x4*>(p + (size_t)i * xC) : k;
+                v[u] = i < Pn ? *reinterpret_cast<const f32x4*>(p + (size_t)i * xC) : k;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                if (i0 + NPL * u < P) {
+                if (i0 + NPL * u < Pn) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const double d = (double)(eab_prelu(v[u][j], a[j]) - k[j]);
@@ -110,8 +114,8 @@ __global__ __launch_bounds__(16 * NPL) void in_stats_kernel(const float* __restr
                 qq += red[1][r][threadIdx.x];
             }
             const float kk = eab_prelu(x[(size_t)b * P * xC + (cc % xC)], slope ? slope[cc] : 1.0f);
-            const double mean_s = ss / P;
-            double var = qq / P - mean_s * mean_s;
+            const double mean_s = ss / Pn;
+            double var = qq / Pn - mean_s * mean_s;
             if (var < 0.0) var = 0.0;
             const double mean = mean_s + (double)kk;
             const double rstd = 1.0 / sqrt(var + (double)eps);
@@ -139,17 +143,17 @@ __global__ __launch_bounds__(16 * NPL) void in_stats_kernel(const float* __restr
             // several views (xC < C): every view is its own contiguous [B][P][xC] tensor, one behind the other
             const int yC = xC < C ? xC : C;
             float* yp = y + (size_t)(c / yC) * gridDim.x * P * yC + (size_t)b * P * yC + (c % yC);
-            for (int i0 = pl; i0 < P; i0 += 4 * NPL) {
+            for (int i0 = pl; i0 < Pn; i0 += 4 * NPL) {
                 f32x4 v[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int i = i0 + NPL * u;
-                    v[u] = i < P ? *reinterpret_cast<const f32x4*>(p + (size_t)i * xC) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    v[u] = i < Pn ? *reinterpret_cast<const f32x4*>(p + (size_t)i * xC) : f32x4{0.f, 0.f, 0.f, 0.f};
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int i = i0 + NPL * u;
-                    if (i < P) {
+                    if (i < Pn) {
                         f32x4 o;
 #pragma unroll
                         for (int j = 0; j < 4; ++j) o[j] = fmaf(eab_prelu(v[u][j], a[j]), sc4[j], sh4[j]);
@@ -161,11 +165,20 @@ __global__ __launch_bounds__(16 * NPL) void in_stats_kernel(const float* __restr
     }
 }
 
+// lens != NULL needs the frame count T the P positions divide into (lens == NULL: T is not read)
+#define TR_CHECK_LENS(lens_, P_, T_) EAB_CHECK_ARG(!(lens_) || ((T_) > 0 && (P_) % (T_) == 0))
+
 extern "C" int eab_train_in_stats_f32(const float* x, const float* slope, int B, int P, int C, float eps, const float* gamma,
                                       const float* beta, float* xf, float* mr, eab_stream_t stream) {
+    return eab_train_in_stats_lens_f32(x, slope, B, P, C, eps, gamma, beta, xf, mr, nullptr, 0, stream);
+}
+
+extern "C" int eab_train_in_stats_lens_f32(const float* x, const float* slope, int B, int P, int C, float eps, const float* gamma,
+                                           const float* beta, float* xf, float* mr, const int32_t* lens, int T, eab_stream_t stream) {
     EAB_CHECK_ARG(x && gamma && beta && xf && mr && B > 0 && P > 0 && C > 0 && (C % 4) == 0 && B <= 65535);
+    TR_CHECK_LENS(lens, P, T);
     hipLaunchKernelGGL((in_stats_kernel<false, 16>), dim3(B, (C + 63) / 64), dim3(TR_THREADS), 0, eab_stream(stream), x, slope, P, C, eps,
-                       gamma, beta, xf, mr, nullptr, C);
+                       gamma, beta, xf, mr, nullptr, C, lens, T);
     EAB_RETURN_LAUNCH_STATUS();
 }
 
@@ -173,14 +186,21 @@ extern "C" int eab_train_in_stats_f32(const float* x, const float* slope, int B,
 // backward pass, and the normalised output.  One workgroup per (b, 64 channels) walks its P positions twice.
 extern "C" int eab_train_in1d_f32(const float* x, const float* slope, int B, int P, int C, float eps, const float* gamma,
                                   const float* beta, float* xf, float* mr, float* y, eab_stream_t stream) {
+    return eab_train_in1d_lens_f32(x, slope, B, P, C, eps, gamma, beta, xf, mr, y, nullptr, 0, stream);
+}
+
+extern "C" int eab_train_in1d_lens_f32(const float* x, const float* slope, int B, int P, int C, float eps, const float* gamma,
+                                       const float* beta, float* xf, float* mr, float* y, const int32_t* lens, int T,
+                                       eab_stream_t stream) {
     EAB_CHECK_ARG(x && slope && gamma && beta && xf && mr && y && B > 0 && P > 0 && C > 0 && (C % 4) == 0 && B <= 65535);
+    TR_CHECK_LENS(lens, P, T);
     // few workgroups (B * C/64) each walking its whole slab twice: 1024 threads per workgroup when the grid cannot fill the chip
     if ((long long)B * ((C + 63) / 64) < 256 && P >= 256)
         hipLaunchKernelGGL((in_stats_kernel<true, 64>), dim3(B, (C + 63) / 64), dim3(1024), 0, eab_stream(stream), x, slope, P, C, eps,
-                           gamma, beta, xf, mr, y, C);
+                           gamma, beta, xf, mr, y, C, lens, T);
     else
         hipLaunchKernelGGL((in_stats_kernel<true, 16>), dim3(B, (C + 63) / 64), dim3(TR_THREADS), 0, eab_stream(stream), x, slope, P, C,
-                           eps, gamma, beta, xf, mr, y, C);
+                           eps, gamma, beta, xf, mr, y, C, lens, T);
     EAB_RETURN_LAUNCH_STATUS();
 }
 
@@ -189,14 +209,21 @@ extern "C" int eab_train_in1d_f32(const float* x, const float* slope, int B, int
 // 559-560, in one launch).
 extern "C" int eab_train_in1d_multi_f32(const float* x, const float* slope, int B, int P, int C, int xC, float eps,
                                         const float* gamma, const float* beta, float* xf, float* mr, float* y, eab_stream_t stream) {
+    return eab_train_in1d_multi_lens_f32(x, slope, B, P, C, xC, eps, gamma, beta, xf, mr, y, nullptr, 0, stream);
+}
+
+extern "C" int eab_train_in1d_multi_lens_f32(const float* x, const float* slope, int B, int P, int C, int xC, float eps,
+                                             const float* gamma, const float* beta, float* xf, float* mr, float* y,
+                                             const int32_t* lens, int T, eab_stream_t stream) {
+    TR_CHECK_LENS(lens, P, T);
     EAB_CHECK_ARG(x && slope && gamma && beta && xf && mr && y && B > 0 && P > 0 && C > 0 && xC > 0 && (xC % 4) == 0 && (C % xC) == 0 &&
                   B <= 65535);
     if ((long long)B * ((C + 63) / 64) < 256 && P >= 256)
         hipLaunchKernelGGL((in_stats_kernel<true, 64>), dim3(B, (C + 63) / 64), dim3(1024), 0, eab_stream(stream), x, slope, P, C, eps,
-                           gamma, beta, xf, mr, y, xC);
+                           gamma, beta, xf, mr, y, xC, lens, T);
     else
         hipLaunchKernelGGL((in_stats_kernel<true, 16>), dim3(B, (C + 63) / 64), dim3(TR_THREADS), 0, eab_stream(stream), x, slope, P, C,
-                           eps, gamma, beta, xf, mr, y, xC);
+                           eps, gamma, beta, xf, mr, y, xC, lens, T);
     EAB_RETURN_LAUNCH_STATUS();
 }
 
@@ -311,9 +338,13 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_reduce_kernel(const float
                                                                      const float* __restrict__ mr, const float* __restrict__ gamma,
                                                                      const float* __restrict__ beta, const float* __restrict__ slope,
                                                                      float* __restrict__ sums, int P, int C, int chunk,
-                                                                     int xC, const float* __restrict__ dy1) {
+                                                                     int xC, const float* __restrict__ dy1,
+                                                                     const int* __restrict__ lens, int T) {
     __shared__ f32x4 red[3][NB_ROWS][16];
     const int b = blockIdx.z, cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
+    // per-utterance lengths: the sums run over the first Pn positions (in_stats_kernel); a block wholly behind them adds nothing
+    const int Pn = lens ? min(lens[b], T) * (P / T) : P;
+    if (blockIdx.x * chunk >= Pn) return;
     const int c = blockIdx.y * 64 + cl * 4;
     f32x4 A = {0.f, 0.f, 0.f, 0.f}, Q = A, S = A;
     if (c < C) {
@@ -324,7 +355,7 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_reduce_kernel(const float
         const float mean[4] = {m01[0], m01[2], m23[0], m23[2]}, rstd[4] = {m01[1], m01[3], m23[1], m23[3]};
         const f32x4 g = mr ? *reinterpret_cast<const f32x4*>(gamma + c) : ones, be = mr ? *reinterpret_cast<const f32x4*>(beta + c) : zeros,
                     a = *reinterpret_cast<const f32x4*>(slope + c);
-        const int p0 = blockIdx.x * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+        const int p0 = blockIdx.x * chunk, p1 = p0 + chunk < Pn ? p0 + chunk : Pn;
         // xC < C: views (see in_stats_kernel): view v's output gradient is its own [B][P][xC] tensor (dy, dy1)
         const size_t xbase = (size_t)b * P * xC + (c % xC);
         const float* dyp = xC < C ? (c < xC ? dy : dy1) + xbase : dy + (size_t)b * P * C + c;
@@ -389,9 +420,12 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_apply_kernel(const float*
                                                                     float* __restrict__ sums, const float* __restrict__ acc_in,
                                                                     float* __restrict__ dx, float* __restrict__ dgamma,
                                                                     float* __restrict__ dbeta, float* __restrict__ dslope, int P, int C,
-                                                                    int chunk, int dx_bf16) {
+                                                                    int chunk, int dx_bf16, const int* __restrict__ lens, int T) {
     __shared__ f32x4 red[NB_ROWS][16];
     const int b = blockIdx.z, B = gridDim.z, cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
+    // per-utterance lengths: Pn positions count (the divisor included); rows behind them are neither read nor written
+    const int Pn = lens ? min(lens[b], T) * (P / T) : P;
+    if (blockIdx.x * chunk >= Pn) return;
     const int c = blockIdx.y * 64 + cl * 4;
     f32x4 S = {0.f, 0.f, 0.f, 0.f};
     if (c < C) {
@@ -402,7 +436,7 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_apply_kernel(const float*
         const float mean[4] = {m01[0], m01[2], m23[0], m23[2]}, rstd[4] = {m01[1], m01[3], m23[1], m23[3]};
         const f32x4 g = mr ? *reinterpret_cast<const f32x4*>(gamma + c) : ones, be = mr ? *reinterpret_cast<const f32x4*>(beta + c) : zeros,
                     a = *reinterpret_cast<const f32x4*>(slope + c);
-        const float inv_p = mr ? 1.0f / (float)P : 0.0f;
+        const float inv_p = mr ? 1.0f / (float)Pn : 0.0f;
         float Am[4], Qm[4], k[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -420,7 +454,7 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_apply_kernel(const float*
                 if (MODE == EAB_XF_NORM_PRELU) atomicAdd(&dslope[c + j], v[2]);
             }
         }
-        const int p0 = blockIdx.x * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+        const int p0 = blockIdx.x * chunk, p1 = p0 + chunk < Pn ? p0 + chunk : Pn;
         const size_t base = (size_t)b * P * C + c;
         for (int i0 = p0 + pl; i0 < p1; i0 += NB_ROWS * NB_UNROLL) {
             f32x4 xq[NB_UNROLL], dq[NB_UNROLL], aq[NB_UNROLL];
@@ -484,16 +518,19 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_apply_multi_kernel(const 
                                                                           const float* __restrict__ slope, const float* __restrict__ sums,
                                                                           const float* __restrict__ acc_in, float* __restrict__ dx,
                                                                           float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                                          float* __restrict__ dslope, int P, int C, int xC, int chunk) {
+                                                                          float* __restrict__ dslope, int P, int C, int xC, int chunk,
+                                                                          const int* __restrict__ lens, int T) {
     __shared__ f32x4 red[2][NB_ROWS][16];
     const int b = blockIdx.z, cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
+    const int Pn = lens ? min(lens[b], T) * (P / T) : P;          // (see norm_bwd_apply_kernel)
+    if (blockIdx.x * chunk >= Pn) return;
     const int c = blockIdx.y * 64 + cl * 4;                        // input channel
     const int NV = C / xC;                                         // 2 (host-checked: <= 2)
     f32x4 S[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     if (c < xC) {
         float mean[2][4], k[2][4], Am[2][4], Qm[2][4];
         f32x4 a[2];
-        const float inv_p = 1.0f / (float)P;
+        const float inv_p = 1.0f / (float)Pn;
         for (int v = 0; v < NV; ++v) {
             const int cv = c + v * xC;
             const float* mp = &mr[((size_t)b * C + cv) * 2];
@@ -514,7 +551,7 @@ __global__ __launch_bounds__(TR_THREADS) void norm_bwd_apply_multi_kernel(const 
                 }
             }
         }
-        const int p0 = blockIdx.x * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+        const int p0 = blockIdx.x * chunk, p1 = p0 + chunk < Pn ? p0 + chunk : Pn;
         const size_t xbase = (size_t)b * P * xC + c;
         for (int i = p0 + pl; i < p1; i += NB_ROWS) {
             const f32x4 xv = *reinterpret_cast<const f32x4*>(&x[xbase + (size_t)i * xC]);
@@ -576,6 +613,15 @@ static inline int nb_chunk(int P, int B, int C) {
 extern "C" int eab_train_norm_bwd_f32(const float* dy, const float* x, const float* mr, const float* gamma, const float* beta,
                                       const float* slope, float* sums, const float* acc_in, float* dx, float* dgamma,
                                       float* dbeta, float* dslope, int B, int P, int C, int mode, eab_stream_t stream) {
+    return eab_train_norm_bwd_lens_f32(dy, x, mr, gamma, beta, slope, sums, acc_in, dx, dgamma, dbeta, dslope, B, P, C, mode, nullptr, 0,
+                                       stream);
+}
+
+extern "C" int eab_train_norm_bwd_lens_f32(const float* dy, const float* x, const float* mr, const float* gamma, const float* beta,
+                                           const float* slope, float* sums, const float* acc_in, float* dx, float* dgamma,
+                                           float* dbeta, float* dslope, int B, int P, int C, int mode, const int32_t* lens, int T,
+                                           eab_stream_t stream) {
+    TR_CHECK_LENS(lens, P, T);
     // mr == NULL (then gamma, beta, dgamma, dbeta are not touched): no norm in front of the PReLU, NORM_PRELU order only
     EAB_CHECK_ARG(dy && x && slope && sums && dx && dslope);
     EAB_CHECK_ARG(mr ? (gamma && beta && dgamma && dbeta) : true);
@@ -595,19 +641,19 @@ extern "C" int eab_train_norm_bwd_f32(const float* dy, const float* x, const flo
                            (long long)NB_SHARDS * B * C);
     if (mode == EAB_XF_NORM_PRELU)
         hipLaunchKernelGGL(norm_bwd_reduce_kernel<EAB_XF_NORM_PRELU>, grid, dim3(TR_THREADS), 0, s, dy, x, mr, gamma, beta, slope, sums, P,
-                           C, chunk, C, nullptr);
+                           C, chunk, C, nullptr, lens, T);
     else
         hipLaunchKernelGGL(norm_bwd_reduce_kernel<EAB_XF_PRELU_NORM>, grid, dim3(TR_THREADS), 0, s, dy, x, mr, gamma, beta, slope, sums, P,
-                           C, chunk, C, nullptr);
+                           C, chunk, C, nullptr, lens, T);
     // parameter gradients inside the apply pass: always for NORM_PRELU (all three sums are final after the reduce pass); for
     // PRELU_NORM when its slope sums can go straight into dslope (<= 256 workgroups per address: the S-TCN's slabs)
     const bool merged = mode == EAB_XF_NORM_PRELU || (long long)grid.x * B <= 256;
     if (mode == EAB_XF_NORM_PRELU)
         hipLaunchKernelGGL(norm_bwd_apply_kernel<EAB_XF_NORM_PRELU>, grid, dim3(TR_THREADS), 0, s, dy, x, mr, gamma, beta, slope, sums,
-                           acc_in, dx, merged ? dgamma : nullptr, dbeta, dslope, P, C, chunk, dx_bf16);
+                           acc_in, dx, merged ? dgamma : nullptr, dbeta, dslope, P, C, chunk, dx_bf16, lens, T);
     else
         hipLaunchKernelGGL(norm_bwd_apply_kernel<EAB_XF_PRELU_NORM>, grid, dim3(TR_THREADS), 0, s, dy, x, mr, gamma, beta, slope, sums,
-                           acc_in, dx, merged ? dgamma : nullptr, dbeta, dslope, P, C, chunk, dx_bf16);
+                           acc_in, dx, merged ? dgamma : nullptr, dbeta, dslope, P, C, chunk, dx_bf16, lens, T);
     if (!merged) hipLaunchKernelGGL(norm_bwd_params_kernel, dim3((C + 63) / 64), dim3(64), 0, s, sums, B, C, dgamma, dbeta, dslope);
     EAB_RETURN_LAUNCH_STATUS();
 }
@@ -619,6 +665,15 @@ extern "C" int eab_train_norm_bwd_f32(const float* dy, const float* x, const flo
 extern "C" int eab_train_norm_bwd_multi_f32(const float* dy0, const float* dy1, const float* x, const float* mr, const float* gamma,
                                             const float* slope, float* sums, const float* acc_in, float* dx, float* dgamma,
                                             float* dbeta, float* dslope, int B, int P, int xC, eab_stream_t stream) {
+    return eab_train_norm_bwd_multi_lens_f32(dy0, dy1, x, mr, gamma, slope, sums, acc_in, dx, dgamma, dbeta, dslope, B, P, xC, nullptr, 0,
+                                             stream);
+}
+
+extern "C" int eab_train_norm_bwd_multi_lens_f32(const float* dy0, const float* dy1, const float* x, const float* mr, const float* gamma,
+                                                 const float* slope, float* sums, const float* acc_in, float* dx, float* dgamma,
+                                                 float* dbeta, float* dslope, int B, int P, int xC, const int32_t* lens, int T,
+                                                 eab_stream_t stream) {
+    TR_CHECK_LENS(lens, P, T);
     EAB_CHECK_ARG(dy0 && dy1 && x && mr && gamma && slope && sums && dx && dgamma && dbeta && dslope);
     EAB_CHECK_ARG(B > 0 && P > 0 && xC > 0 && (xC % 4) == 0 && B <= 65535);
     const int C = 2 * xC;
@@ -627,9 +682,9 @@ extern "C" int eab_train_norm_bwd_multi_f32(const float* dy0, const float* dy1, 
     const int chunk = nb_chunk(P, B, C);
     hipStream_t s = eab_stream(stream);
     hipLaunchKernelGGL(norm_bwd_reduce_kernel<EAB_XF_PRELU_NORM>, dim3((P + chunk - 1) / chunk, (C + 63) / 64, B), dim3(TR_THREADS), 0, s,
-                       dy, x, mr, gamma, beta, slope, sums, P, C, chunk, xC, dy1);
+                       dy, x, mr, gamma, beta, slope, sums, P, C, chunk, xC, dy1, lens, T);
     hipLaunchKernelGGL(norm_bwd_apply_multi_kernel, dim3((P + chunk - 1) / chunk, (xC + 63) / 64, B), dim3(TR_THREADS), 0, s, dy, dy1, x,
-                       mr, gamma, slope, sums, acc_in, dx, dgamma, dbeta, dslope, P, C, xC, chunk);
+                       mr, gamma, slope, sums, acc_in, dx, dgamma, dbeta, dslope, P, C, xC, chunk, lens, T);
     EAB_RETURN_LAUNCH_STATUS();
 }
 
@@ -836,7 +891,9 @@ extern "C" int eab_colsum_f32(const float* x, float* out, long long rows, int N,
 // Four lanes per TF bin (lane p: microphones p, p+4, ...), 32-bit bin arithmetic with one division per bin: see
 // filter_sum_kernel (csrc/filter_sum.hip) -- one thread per bin with four 64-bit divisions was the first version of these too.
 __global__ __launch_bounds__(TR_THREADS) void filter_sum_ld_kernel(const float* __restrict__ w, const float* __restrict__ x,
-                                                                   float* __restrict__ y, unsigned TF, int M, int ld, unsigned bins) {
+                                                                   float* __restrict__ y, unsigned TF, int M, int ld, unsigned bins,
+                                                                   const int* __restrict__ lens, unsigned F) {
+    // lens: output frames t >= lens[b] are written as exact zeros BY SELECTION (whatever the padding rows of w and x hold)
     const unsigned p = threadIdx.x & 3, stride = gridDim.x * (TR_THREADS / 4);
     for (unsigned base = blockIdx.x * (TR_THREADS / 4); base < bins; base += stride) {   // workgroup-uniform trip count
         const unsigned bin = base + (threadIdx.x >> 2);
@@ -855,8 +912,9 @@ __global__ __launch_bounds__(TR_THREADS) void filter_sum_ld_kernel(const float* 
         yr += __shfl_xor(yr, 2); yi += __shfl_xor(yi, 2);
         if (valid && p == 0) {
             const unsigned b = bin / TF, pos = bin - b * TF;
-            y[(size_t)(2 * b) * TF + pos] = yr;
-            y[(size_t)(2 * b + 1) * TF + pos] = yi;
+            const bool pad = lens && pos >= (unsigned)lens[b] * F;
+            y[(size_t)(2 * b) * TF + pos] = pad ? 0.0f : yr;
+            y[(size_t)(2 * b + 1) * TF + pos] = pad ? 0.0f : yi;
         }
     }
 }
@@ -884,11 +942,16 @@ static inline unsigned fs_grid(long long bins) {
 
 // w rows of `ld` floats (the first 2M used): the training program keeps the beam-forming weights in a 64-column tile
 extern "C" int eab_filter_sum_ld_f32(const float* w, const float* x, float* y, int B, int T, int F, int M, int ld, eab_stream_t stream) {
+    return eab_filter_sum_ld_lens_f32(w, x, y, B, T, F, M, ld, nullptr, stream);
+}
+
+extern "C" int eab_filter_sum_ld_lens_f32(const float* w, const float* x, float* y, int B, int T, int F, int M, int ld, const int32_t* lens,
+                                          eab_stream_t stream) {
     EAB_CHECK_ARG(w && x && y && B > 0 && T > 0 && F > 0 && M > 0 && ld >= 2 * M && (ld % 2) == 0);
     const long long bins = (long long)B * T * F;
     EAB_CHECK_ARG(bins < (1ll << 30));
     hipLaunchKernelGGL(filter_sum_ld_kernel, dim3(fs_grid(bins)), dim3(TR_THREADS), 0, eab_stream(stream), w, x, y,
-                       (unsigned)((long long)T * F), M, ld, (unsigned)bins);
+                       (unsigned)((long long)T * F), M, ld, (unsigned)bins, lens, (unsigned)F);
     EAB_RETURN_LAUNCH_STATUS();
 }
 
@@ -928,7 +991,9 @@ __global__ __launch_bounds__(TR_THREADS) void layernorm_fwd_kernel(const float* 
 __global__ __launch_bounds__(TR_THREADS) void layernorm_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                    const float* __restrict__ mr, const float* __restrict__ g,
                                                                    float* __restrict__ dx, float* __restrict__ dg,
-                                                                   float* __restrict__ db, long long rows) {
+                                                                   float* __restrict__ db, long long rows,
+                                                                   const int* __restrict__ lens, int T, int F) {
+    // lens (rows = [B][T][F]): dg and db sum the rows of frames t < lens[b] only -- by selection; dx is row-local
     __shared__ float red[2][16][64];
     const int lc = (threadIdx.x & 15) * 4, rl = threadIdx.x >> 4;
     const f32x4 g4 = *reinterpret_cast<const f32x4*>(g + lc);
@@ -937,13 +1002,19 @@ __global__ __launch_bounds__(TR_THREADS) void layernorm_bwd_kernel(const float* 
     for (long long r = (long long)blockIdx.x * 16 + rl; r < rows; r += (long long)gridDim.x * 16) {
         const f32x4 d = *reinterpret_cast<const f32x4*>(&dy[r * 64 + lc]), v = *reinterpret_cast<const f32x4*>(&x[r * 64 + lc]);
         const float2 m = *reinterpret_cast<const float2*>(&mr[r * 2]);
+        bool live = true;
+        if (lens) {                                                // (rows < 2^31 with lengths: host check)
+            const unsigned bt = (unsigned)r / (unsigned)F, b = bt / (unsigned)T;      // bt = b * T + t
+            live = (int)(bt - b * (unsigned)T) < lens[b];
+        }
         f32x4 xh, dh;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             xh[j] = (v[j] - m.x) * m.y;
             dh[j] = d[j] * g4[j];
-            sg[j] += d[j] * xh[j];
-            sb[j] += d[j];
+            const float ds = live ? d[j] : 0.0f, xs = live ? xh[j] : 0.0f;     // (a padding row adds 0 * 0, whatever it holds)
+            sg[j] += ds * xs;
+            sb[j] += ds;
         }
         const float A = eab_row_sum((dh[0] + dh[1]) + (dh[2] + dh[3])) * (1.0f / 64.0f);
         const float Q = eab_row_sum((dh[0] * xh[0] + dh[1] * xh[1]) + (dh[2] * xh[2] + dh[3] * xh[3])) * (1.0f / 64.0f);
@@ -978,9 +1049,17 @@ extern "C" int eab_layernorm64_fwd_f32(const float* x, const float* g, const flo
 
 extern "C" int eab_layernorm64_bwd_f32(const float* dy, const float* x, const float* mr, const float* g, float* dx, float* dg,
                                        float* db, long long rows, eab_stream_t stream) {
+    return eab_layernorm64_bwd_lens_f32(dy, x, mr, g, dx, dg, db, rows, nullptr, 0, 0, stream);
+}
+
+extern "C" int eab_layernorm64_bwd_lens_f32(const float* dy, const float* x, const float* mr, const float* g, float* dx, float* dg,
+                                            float* db, long long rows, const int32_t* lens, int B, int T, eab_stream_t stream) {
     EAB_CHECK_ARG(dy && x && mr && g && dx && dg && db && rows > 0);
+    EAB_CHECK_ARG(!lens || (B > 0 && T > 0 && rows % ((long long)B * T) == 0 && rows < (1ll << 31)));
+    const int F = lens ? (int)(rows / ((long long)B * T)) : 1;
     long long grid = (rows + 15) / 16;
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)grid), dim3(TR_THREADS), 0, eab_stream(stream), dy, x, mr, g, dx, dg, db, rows);
+    hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)grid), dim3(TR_THREADS), 0, eab_stream(stream), dy, x, mr, g, dx, dg, db, rows,
+                       lens, lens ? T : 1, F);
     EAB_RETURN_LAUNCH_STATUS();
 }

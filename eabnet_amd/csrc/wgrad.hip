@@ -65,6 +65,19 @@ struct WgRow {
         }
         return wrap;
     }
+    // ... also telling whether the row moved on to another batch element (the kernels with per-utterance lengths)
+    __device__ __forceinline__ bool step(int a, int rem, int T, int No, bool& moved) {
+        o += rem;
+        t += a;
+        const bool wrap = o >= No;
+        if (wrap) {
+            o -= No;
+            ++t;
+        }
+        moved = t >= T;
+        while (t >= T) t -= T;
+        return wrap;
+    }
 };
 
 // One launch serves up to WG_MAXB weight gradients of IDENTICAL geometry (the 18 S-TCMs' in/left/right/out convolutions, the
@@ -79,11 +92,33 @@ struct WgBatch {
     const float* src1[WG_MAXB];
     float* dw[WG_MAXB];
     float* dbias[WG_MAXB];
+    // per-utterance frame counts [B] (device) or NULL: a row (b, t, o) with t >= lens[b] is padding -- invalid for both operands
+    // and for dbias (it reads 0 like a row past the group's end), and a row group wholly in padding adds nothing
+    const int32_t* lens;
 };
+
+// frames of utterance b that count (b may run past the batch behind the last row: clamped)
+__device__ __forceinline__ int wg_lim(const int32_t* __restrict__ lens, int b, int B, int T) {
+    return lens ? min(lens[b < B ? b : B - 1], T) : T;
+}
+// ... of the utterance that holds row r (a walker that moved on to another batch element asks again: rare, so the division
+// costs nothing and the walker needs no register for b)
+__device__ __forceinline__ int wg_lim_of_row(const int32_t* __restrict__ lens, long long r, int B, int T, int No) {
+    return wg_lim(lens, (int)(r / ((long long)T * No)), B, T);
+}
+
+// a row group [r_begin, r_end) that lies inside ONE utterance and starts at or past its length holds padding rows only
+__device__ __forceinline__ bool wg_all_padding(const int32_t* __restrict__ lens, long long r_begin, long long r_end, int B, int T, int No) {
+    if (!lens || r_begin >= r_end) return false;
+    const long long rows_b = (long long)T * No;
+    const int b0 = (int)(r_begin / rows_b), b1 = (int)((r_end - 1) / rows_b);
+    return b0 == b1 && (int)((r_begin - b0 * rows_b) / No) >= wg_lim(lens, b0, B, T);
+}
 
 // VEC (compile time): channel counts are multiples of 4 -> 16-byte gathers; false only for the network input of an odd
 // number of microphones.  A run-time flag around the operand loads breaks their burst (see wgrad_bf_kernel).
-template <int TN, int TC, bool VEC>
+// LENS (compile time): per-utterance lengths (WgBatch.lens).  The instances without them are the kernels as they always were.
+template <int TN, int TC, bool VEC, bool LENS>
 __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
     using Smem = WgSmem<TN, TC>;
     const eab_wgrad_desc& d = bt.d;
@@ -107,6 +142,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
     const long long r_end = r_begin + d.rows_per_wg < R ? r_begin + d.rows_per_wg : R;
     const int col0 = blockIdx.y * TC, n0 = blockIdx.z * TN;
     const int Ctot = d.C0 + d.C1, UPT = (Ctot + 15) >> 4, NU = d.ntaps * UPT;
+    if (LENS && wg_all_padding(bt.lens, r_begin, r_end, d.B, d.T, d.No)) return;      // (workgroup-uniform) nothing to add: no atomics
 
     // ---- staging roles --------------------------------------------------------------------------------
     // A (dz): thread -> row (tid>>5) + 8p (TN = 128) / tid>>4 (TN = 64), float4 column
@@ -146,14 +182,17 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
     const __amdgpu_buffer_rsrc_t rs_s1 = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(m_src1 ? m_src1 : m_src0), 0, m_src1 ? (unsigned)((size_t)d.B * d.T * d.Fin * d.C1 * 4) : 0u, 0x00020000);
     WgRow ra_[AP], rb_;
+    int limA[AP], limB;                                          // frames that count in the walker's utterance (refreshed when b moves)
     unsigned offA[AP];
     int offB[BP];                                                // (may be negative while the tap is out of range: unused then)
 #pragma unroll
     for (int p = 0; p < AP; ++p) {
         ra_[p].init(r_begin + a_row + 8 * p, d.T, d.No);
+        limA[p] = LENS ? wg_lim(bt.lens, ra_[p].b, d.B, d.T) : d.T;
         offA[p] = (unsigned)(((((size_t)ra_[p].b * d.T + ra_[p].t) * d.Fz + (size_t)ra_[p].o * d.ostride + d.ophase) * d.N + n0 + a_c4 * 4) * 4);
     }
     rb_.init(r_begin + b_row, d.T, d.No);
+    limB = LENS ? wg_lim(bt.lens, rb_.b, d.B, d.T) : d.T;
     const unsigned dA0 = (unsigned)((adv_a * d.Fz + adv_r * d.ostride) * d.N * 4), dA1 = (unsigned)((d.Fz - d.No * d.ostride) * d.N * 4);
     int dB0[BP], dB1[BP];
     bool b_second[BP];
@@ -175,15 +214,21 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
     auto fetch = [&](long long r0) {
 #pragma unroll
         for (int p = 0; p < AP; ++p) {
-            const bool ok = r0 + a_row + 8 * p < r_end;
+            const bool ok = r0 + a_row + 8 * p < r_end && (!LENS || ra_[p].t < limA[p]);
             ra[p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, ok ? offA[p] : EAB_OOB, 0, 0));
-            offA[p] += dA0 + (ra_[p].step(adv_a, adv_r, d.T, d.No) ? dA1 : 0u);
+            if constexpr (LENS) {
+                bool moved;
+                offA[p] += dA0 + (ra_[p].step(adv_a, adv_r, d.T, d.No, moved) ? dA1 : 0u);
+                if (moved) limA[p] = wg_lim_of_row(bt.lens, r0 + WG_ROWS + a_row + 8 * p, d.B, d.T, d.No);
+            } else {
+                offA[p] += dA0 + (ra_[p].step(adv_a, adv_r, d.T, d.No) ? dA1 : 0u);
+            }
         }
-        const bool rok = r0 + b_row < r_end;
+        const bool rok = r0 + b_row < r_end && (!LENS || rb_.t < limB);
 #pragma unroll
         for (int j = 0; j < BP; ++j) {
             const int tt = rb_.t + tdt[j], fi = rb_.o * d.istride + tio[j];
-            const bool ok = rok && b_ok[j] && tt >= 0 && tt < d.T && fi >= 0 && fi < d.Fin;
+            const bool ok = rok && b_ok[j] && tt >= 0 && tt < (LENS ? limB : d.T) && fi >= 0 && fi < d.Fin;
             const unsigned off = ok ? (unsigned)offB[j] : EAB_OOB;
             if (vec_ok) {
                 rb[j] = __builtin_bit_cast(f32x4, b_second[j] ? __builtin_amdgcn_raw_buffer_load_b128(rs_s1, off, 0, 0)
@@ -195,7 +240,14 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
                                                              rs_s0, (ok && b_cc[j] + e < b_Cs[j]) ? off + 4u * e : EAB_OOB, 0, 0));
             }
         }
-        const bool wrap = rb_.step(adv_a, adv_r, d.T, d.No);
+        bool wrap;
+        if constexpr (LENS) {
+            bool moved;
+            wrap = rb_.step(adv_a, adv_r, d.T, d.No, moved);
+            if (moved) limB = wg_lim_of_row(bt.lens, r0 + WG_ROWS + b_row, d.B, d.T, d.No);
+        } else {
+            wrap = rb_.step(adv_a, adv_r, d.T, d.No);
+        }
 #pragma unroll
         for (int j = 0; j < BP; ++j) offB[j] += dB0[j] + (wrap ? dB1[j] : 0);
     };
@@ -288,7 +340,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_kernel(const WgBatch bt) {
 #define WGB_S 9
 
 // HALF (compile time, so that the operand loads of a stage stay one straight-line burst): bit 0 = dz, bit 1 = x stored as bf16
-template <int TN, int TC, int HALF, bool VEC>
+template <int TN, int TC, int HALF, bool VEC, bool LENS>
 __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) {
     constexpr int MI = TN / 64, NJ = TC / 64;
     __shared__ unsigned a_t[2][TN * WGB_S];
@@ -311,6 +363,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
     const long long r_end = r_begin + d.rows_per_wg < R ? r_begin + d.rows_per_wg : R;
     const int col0 = blockIdx.y * TC, n0 = blockIdx.z * TN;
     const int Ctot = d.C0 + d.C1, UPT = (Ctot + 15) >> 4, NU = d.ntaps * UPT;
+    if (LENS && wg_all_padding(bt.lens, r_begin, r_end, d.B, d.T, d.No)) return;      // (workgroup-uniform) nothing to add: no atomics
 
     const int rp = tid >> 5, c4 = tid & 31;                        // row pair of the stage, float4 column
     const bool a_live = c4 * 4 < TN, b_live = c4 * 4 < TC;
@@ -344,11 +397,13 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
     const __amdgpu_buffer_rsrc_t rs_src = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(b_src), 0, (unsigned)((size_t)d.B * d.T * d.Fin * b_Cs * eszB), 0x00020000);
     WgRow rw[2];
+    int lim[2];                                                   // frames that count in the walker's utterance (see wgrad_kernel)
     unsigned offA[2];
     int offB[2];
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
         rw[e].init(r_begin + 2 * rp + e, d.T, d.No);
+        lim[e] = LENS ? wg_lim(bt.lens, rw[e].b, d.B, d.T) : d.T;
         const long long bt = (long long)rw[e].b * d.T + rw[e].t;
         offA[e] = (unsigned)((((bt * d.Fz) + (long long)rw[e].o * d.ostride + d.ophase) * d.N + n0 + c4 * 4) * eszA);
         offB[e] = (int)((((bt + tdt) * d.Fin + (long long)rw[e].o * d.istride + tio) * b_Cs + b_cc) * eszB);
@@ -362,7 +417,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
     auto fetch = [&](long long r0) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-            const bool rok = r0 + 2 * rp + e < r_end;
+            const bool rok = r0 + 2 * rp + e < r_end && (!LENS || rw[e].t < lim[e]);
             if (a_half) {                                         // (workgroup-uniform)
                 const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_dz, (rok && a_live) ? offA[e] : EAB_OOB, 0, 0);
                 ra[e] = __builtin_bit_cast(f32x4, u32x4{v[0], v[1], 0u, 0u});
@@ -370,7 +425,7 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
                 ra[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_dz, (rok && a_live) ? offA[e] : EAB_OOB, 0, 0));
             }
             const int tt = rw[e].t + tdt, fi = rw[e].o * d.istride + tio;
-            const bool ok = rok && b_ok && tt >= 0 && tt < d.T && fi >= 0 && fi < d.Fin;
+            const bool ok = rok && b_ok && tt >= 0 && tt < (LENS ? lim[e] : d.T) && fi >= 0 && fi < d.Fin;
             const unsigned off = ok ? (unsigned)offB[e] : EAB_OOB;
             if (b_half) {                                         // (uniform per thread's column block; C % 16 == 0: host check)
                 const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_src, off, 0, 0);
@@ -383,7 +438,14 @@ __global__ __launch_bounds__(WG_THREADS) void wgrad_bf_kernel(const WgBatch bt) 
                     rb[e][q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                              rs_src, (ok && b_cc + q < b_Cs) ? off + 4u * q : EAB_OOB, 0, 0));
             }
-            const bool wrap = rw[e].step(adv_a, adv_r, d.T, d.No);
+            bool wrap;
+            if constexpr (LENS) {
+                bool moved;
+                wrap = rw[e].step(adv_a, adv_r, d.T, d.No, moved);
+                if (moved) lim[e] = wg_lim_of_row(bt.lens, r0 + WG_ROWS + 2 * rp + e, d.B, d.T, d.No);
+            } else {
+                wrap = rw[e].step(adv_a, adv_r, d.T, d.No);
+            }
             offA[e] += dA0 + (wrap ? dA1 : 0u);
             offB[e] += dB0 + (wrap ? dB1 : 0);
         }
@@ -513,6 +575,10 @@ extern "C" int eab_wgrad_batchable(const eab_wgrad_desc* descs, int n, int strid
 }
 
 extern "C" int eab_wgrad_batch_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, eab_stream_t stream) {
+    return eab_wgrad_batch_lens_f32(descs, n, stride_bytes, nullptr, stream);
+}
+
+extern "C" int eab_wgrad_batch_lens_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, const int32_t* lens, eab_stream_t stream) {
     EAB_CHECK_ARG(descs && n >= 1 && n <= WG_MAXB && stride_bytes >= (int)sizeof(eab_wgrad_desc));
     const eab_wgrad_desc* d = descs;
     auto at = [&](int k) { return reinterpret_cast<const eab_wgrad_desc*>(reinterpret_cast<const char*>(descs) + (size_t)k * stride_bytes); };
@@ -564,6 +630,7 @@ extern "C" int eab_wgrad_batch_f32(const eab_wgrad_desc* descs, int n, int strid
     bt.d.rows_per_wg = (int)rpw;
     bt.n = n;
     bt.groups = (int)((R + rpw - 1) / rpw);
+    bt.lens = lens;
     for (int k = 0; k < WG_MAXB; ++k) {
         const eab_wgrad_desc* m = at(k < n ? k : 0);
         bt.dz[k] = m->dz;
@@ -578,33 +645,45 @@ extern "C" int eab_wgrad_batch_f32(const eab_wgrad_desc* descs, int n, int strid
     const bool vec = (d->C0 & 3) == 0;               // 16-byte gathers (compile-time property of the kernel instance)
     if (d->precision == EAB_PREC_BF16) {
         const int half = d->bf16_mask & 3;       // (both sources of a concatenation alike: checked above)
+#define WG_BF_KERNEL(TN_, TC_, H_, V_)                                                                                      \
+    do {                                                                                                                    \
+        if (lens) hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, H_, V_, true>), grid, dim3(WG_THREADS), 0, s, bt);         \
+        else hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, H_, V_, false>), grid, dim3(WG_THREADS), 0, s, bt);             \
+    } while (0)
 #define WG_BF_LAUNCH(TN_, TC_)                                                                                              \
     do {                                                                                                                    \
         if (!vec) {       /* odd channel counts: the network input only, never stored as bf16 (dz may be) */               \
             if (half & 2) return EAB_EUNSUPPORTED;                                                                          \
-            if (half == 0) hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, 0, false>), grid, dim3(WG_THREADS), 0, s, bt);    \
-            else hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, 1, false>), grid, dim3(WG_THREADS), 0, s, bt);              \
-        } else if (half == 0) hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, 0, true>), grid, dim3(WG_THREADS), 0, s, bt);  \
-        else if (half == 1) hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, 1, true>), grid, dim3(WG_THREADS), 0, s, bt);    \
-        else if (half == 2) hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, 2, true>), grid, dim3(WG_THREADS), 0, s, bt);    \
-        else hipLaunchKernelGGL((wgrad_bf_kernel<TN_, TC_, 3, true>), grid, dim3(WG_THREADS), 0, s, bt);                   \
+            if (half == 0) WG_BF_KERNEL(TN_, TC_, 0, false);                                                                \
+            else WG_BF_KERNEL(TN_, TC_, 1, false);                                                                          \
+        } else if (half == 0) WG_BF_KERNEL(TN_, TC_, 0, true);                                                              \
+        else if (half == 1) WG_BF_KERNEL(TN_, TC_, 1, true);                                                                \
+        else if (half == 2) WG_BF_KERNEL(TN_, TC_, 2, true);                                                                \
+        else WG_BF_KERNEL(TN_, TC_, 3, true);                                                                               \
     } while (0)
         if (tn == 128 && tc == 128) WG_BF_LAUNCH(128, 128);
         else if (tn == 128) WG_BF_LAUNCH(128, 64);
         else if (tc == 128) WG_BF_LAUNCH(64, 128);
         else WG_BF_LAUNCH(64, 64);
+#undef WG_BF_KERNEL
 #undef WG_BF_LAUNCH
         EAB_RETURN_LAUNCH_STATUS();
     }
+#define WG_F32_KERNEL(TN_, TC_, V_)                                                                                         \
+    do {                                                                                                                    \
+        if (lens) hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, V_, true>), grid, dim3(WG_THREADS), 0, s, bt);                \
+        else hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, V_, false>), grid, dim3(WG_THREADS), 0, s, bt);                    \
+    } while (0)
 #define WG_F32_LAUNCH(TN_, TC_)                                                                                             \
     do {                                                                                                                    \
-        if (vec) hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, true>), grid, dim3(WG_THREADS), 0, s, bt);                     \
-        else hipLaunchKernelGGL((wgrad_kernel<TN_, TC_, false>), grid, dim3(WG_THREADS), 0, s, bt);                        \
+        if (vec) WG_F32_KERNEL(TN_, TC_, true);                                                                             \
+        else WG_F32_KERNEL(TN_, TC_, false);                                                                                \
     } while (0)
     if (tn == 128 && tc == 128) WG_F32_LAUNCH(128, 128);
     else if (tn == 128) WG_F32_LAUNCH(128, 64);
     else if (tc == 128) WG_F32_LAUNCH(64, 128);
     else WG_F32_LAUNCH(64, 64);
+#undef WG_F32_KERNEL
 #undef WG_F32_LAUNCH
     EAB_RETURN_LAUNCH_STATUS();
 }

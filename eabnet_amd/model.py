@@ -304,6 +304,9 @@ class _HipModule(nn.Module):
         self.max_resident_bytes = 8 << 30
         self._varlen_bound: "OrderedDict[tuple, _Bound]" = OrderedDict()
         self._varlen_version: Dict[tuple, tuple] = {}
+        # lengths= under autograd: False = refused, as always; True = the training programs run with per-utterance
+        # lengths (masked statistics, recurrences and weight gradients) -- EaBNet, is_causal=True, norm_type="IN"
+        self.varlen_training = False
 
     def _param_fingerprint(self) -> tuple:
         """Change detector for the packed weights (runs on every forward).  Every parameter / buffer slot
@@ -380,6 +383,11 @@ class _HipModule(nn.Module):
             cap = bucket_for(T, self._bucket_caps())
             return None if cap is None else (cap, T)
         lens = check_lengths(lengths, B, T)
+        if needs_graph and self.varlen_training:
+            why = self._varlen_training_refusal()
+            if why:
+                raise NotImplementedError(f"{type(self).__name__}: lengths= under autograd with varlen_training: {why}")
+            return T, lens                                       # the exact padded width of the call
         if needs_graph:
             raise _refuse_differentiable(self, "lengths= under autograd (or BatchNorm in train mode)",
                                          "per-utterance lengths are an inference form; training with lengths (masked batch "
@@ -392,6 +400,21 @@ class _HipModule(nn.Module):
             raise NotImplementedError(f"{type(self).__name__}: lengths= with dump_bfw (a test hook of the exact-shape path)")
         cap = bucket_for(T, self._bucket_caps()) if self.length_buckets is not None else None
         return (cap if cap is not None else T), lens
+
+    def _varlen_training_refusal(self) -> str:
+        """why a differentiable call with lengths= cannot run on the masked training programs ('' when it can)"""
+        cfg = self.cfg
+        if isinstance(cfg, prg.GagConfig):
+            return ("GaGNet (and with it EaBNetWithPostNet) has no masked training lowering yet; train the post-filter on "
+                    "equal-length batches")
+        from . import train
+        why = train.varlen_unsupported_reason(cfg)               # norm and causality: one wording, shared with lower_train
+        if why:
+            return why
+        if self.length_buckets is not None:
+            return ("length_buckets together with a differentiable call: the training programs take the exact padded width "
+                    "(set length_buckets = None)")
+        return ""
 
     def varlen_arena_bytes(self) -> Dict[tuple, int]:
         """Activation-arena bytes of every resident length-bucketed program, keyed (B, T_cap, F, device, precision, chains)."""
@@ -421,7 +444,7 @@ class _HipModule(nn.Module):
             lower = self._training_lowering()
             self.training_backend = "hip"
             xs = tuple(x.detach().to(torch.float32).contiguous() for x in inputs)
-            return train.forward_train(self, xs, lower)
+            return train.forward_train(self, xs, lower, lengths=None if (vl is None or lengths is None) else vl[1])
         if not all(x.is_cuda for x in inputs):
             raise _lib.EabError(f"eabnet_amd.{name} inference runs on MI355X only: move the {noun} (and module) to "
                                 "'cuda'. There is no CPU fallback by design.")
@@ -905,6 +928,16 @@ class EaBNetWithPostNet(nn.Module):
     def length_buckets(self, value) -> None:
         self.eabnet.length_buckets = value
         self.postnet.length_buckets = value
+
+    @property
+    def varlen_training(self):
+        """lengths= under autograd, both stages (see EaBNet.varlen_training; the post-filter refuses it with the reason)"""
+        return self.eabnet.varlen_training
+
+    @varlen_training.setter
+    def varlen_training(self, value) -> None:
+        self.eabnet.varlen_training = value
+        self.postnet.varlen_training = value
 
     def forward(self, noisy_stft: torch.Tensor, lengths=None) -> dict:
         """lengths: optional (B,) frame counts, passed to both stages (EaBNet.forward)"""

@@ -109,6 +109,9 @@ def encode(ops: Sequence, bases: Mapping[str, Optional[int]], t_pos: Optional[in
                     ints[0:2] = [nbytes & 0xFFFFFFFF, nbytes >> 32]
             for j, v in enumerate(ints):
                 o.i[j] = _i32(v)
+            if lens is not None:                        # (B, T) of a training op that carries none, for its lengths form
+                for j, v in (getattr(op, "lens_i", None) or {}).items():
+                    o.i[j] = _i32(v)
             for j, r in enumerate(ptrs):
                 o.p[j] = A(r)
             for j, v in enumerate(flts):

@@ -46,7 +46,7 @@ from .program import (NB_SUM_COPIES, NB_SUMS_ZEROED, OP_ADD, OP_CLN_BWD, OP_COLS
 from .spec import NetConfig, gate_key, param_specs
 
 MLP_LD = 64          # the second Linear of w_dnn is run with its 2M rows padded to one 64-column tile
-TRAIN_BOUND_CACHE = 3   # bound training programs kept per module (LRU over (B, T, F, device, precision))
+TRAIN_BOUND_CACHE = 3   # bound training programs kept per module (LRU over (B, T, F, device, precision, varlen))
 
 
 def supported(cfg: NetConfig) -> bool:
@@ -954,10 +954,50 @@ class TrainProgram:
     sync: Dict[str, dict] = field(default_factory=dict)           # per program: op index -> [("fork" | "join", lanes)]
     # BatchNorm (train mode): (norm key, offset of the layer's batch (mean, rstd) table in the activation arena, C, samples)
     bn_layers: List[tuple] = field(default_factory=list)
+    varlen: bool = False                     # the ops that sum or recurse across rows read per-utterance lengths (flag_varlen)
 
 
-def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "f32") -> TrainProgram:
-    return TrainLowering(cfg, B, T, F, precision).build()
+# op kinds that honour eab_op.win.lens in the training programs, with the i[] slots that carry (B, T) where the op has none
+# (written by runtime.encode only together with the lengths pointer); the convolutions carry lens in their own descriptor
+VARLEN_KINDS = {OP_IN_STATS: ("T", 4), OP_NORM_BWD: ("T", 5), OP_LN_BWD: ("BT", 2), OP_LSTM_BWD: None, OP_FILTER_SUM: None,
+                OP_WGRAD: None}
+
+
+def flag_varlen(prog: TrainProgram) -> TrainProgram:
+    """Mark the readers that sum or recurse across rows: runtime.encode hands the lengths pointer of the binding
+    to every op that has a ``win`` attribute.  The op lists themselves do not change; row-local ops stay unflagged (they carry
+    whatever the padding rows hold to padding rows only)."""
+    for op in list(prog.fwd) + list(prog.bwd):
+        if op.kind in VARLEN_KINDS:
+            op.win = False                                       # (no streaming window: the attribute is what encode looks for)
+            slot = VARLEN_KINDS[op.kind]
+            if slot is not None:
+                op.lens_i = {slot[1]: prog.T} if slot[0] == "T" else {slot[1]: prog.B, slot[1] + 1: prog.T}
+    prog.varlen = True
+    return prog
+
+
+def varlen_unsupported_reason(cfg) -> str:
+    """why a configuration cannot train with per-utterance lengths ('' when it can)"""
+    norm = getattr(cfg, "norm_type", "IN")
+    if norm == "BN":
+        return ("norm_type='BN' in train mode needs masked batch statistics and a masked update of the running buffers, "
+                "which are not implemented")
+    if norm == "cLN":
+        return "norm_type='cLN': the three-launch reverse scan of its backward has no per-utterance masks yet"
+    if not cfg.is_causal:
+        return ("is_causal=True is needed -- the non-causal S-TCM taps of the last frames of an utterance read the frames "
+                "after it, so a padded batch cannot reproduce the one-at-a-time result")
+    return ""
+
+
+def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "f32", varlen: bool = False) -> TrainProgram:
+    """varlen: the same op list with the cross-row readers flagged for per-utterance lengths (flag_varlen); T is the padded
+    width.  Configurations outside is_causal=True / norm_type='IN' are refused."""
+    if varlen and varlen_unsupported_reason(cfg):
+        raise NotImplementedError("training with per-utterance lengths: " + varlen_unsupported_reason(cfg))
+    prog = TrainLowering(cfg, B, T, F, precision).build()
+    return flag_varlen(prog) if varlen else prog
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -977,6 +1017,11 @@ class TrainBound(BoundProgram):
         self.ia = torch.from_numpy(prog.ia).to(device)
         self.ib = torch.from_numpy(prog.ib).to(device) if prog.ib is not None else None
         self.inv = torch.from_numpy(prog.inv).to(device)
+        # per-utterance lengths (varlen programs): ONE device array [B] that both op lists -- and so both captured graphs --
+        # read through a fixed pointer; written on the launch stream before the forward, read again by the backward
+        self.lens = torch.full((prog.B,), prog.T, dtype=torch.int32, device=device) if prog.varlen else None
+        if prog.varlen:
+            self.window = {"lens": self.lens.data_ptr()}
         self.serial = 0                     # forward passes run so far: a backward must belong to the latest one
         self.use_graph = True
         self.flat_param_hits = 0            # forward passes that read the parameters from one flat buffer (no torch.cat)
@@ -1108,16 +1153,19 @@ def finish_flat_gradient(gflat: torch.Tensor, sync_group, shapes, dtypes, needs)
     return grads
 
 
-def forward_train(module, inputs: tuple, lower) -> torch.Tensor:
+def forward_train(module, inputs: tuple, lower, lengths=None) -> torch.Tensor:
     """A differentiable forward of ``module`` on its HIP training programs, lowered by ``lower(cfg, B, T, F, precision)``
     (lower_train here, train_gag.lower_train for GaGNet).  ``inputs``: fp32, contiguous, (B, T, F, M, 2) for EaBNet or two
-    (B, 2, T, F) for GaGNet.  Returns the program's output arena ((B, 2, T, F), or (q, B, 2, T, F) for GaGNet)."""
+    (B, 2, T, F) for GaGNet.  Returns the program's output arena ((B, 2, T, F), or (q, B, 2, T, F) for GaGNet).
+    ``lengths`` (checked by model.check_lengths: a list or a device tensor of B frame counts): the program lowered with
+    varlen=True, its lengths array written on the current stream before the forward replay -- no host synchronisation."""
     _lib.load()
     x = inputs[0]
     B, T, F = (x.shape[0], x.shape[1], x.shape[2]) if x.ndim == 5 else (x.shape[0], x.shape[2], x.shape[3])
     cache = module.__dict__.setdefault("_train_bound", {})
     prec = "bf16" if module.precision == "bf16" else "f32"
-    key = (B, T, F, str(x.device), prec)
+    varlen = lengths is not None
+    key = (B, T, F, str(x.device), prec, varlen)
     bound = cache.pop(key, None)
     if bound is None:
         # a small LRU of bound programs (variable-length batches, a smaller last batch, alternating train / validation
@@ -1126,13 +1174,18 @@ def forward_train(module, inputs: tuple, lower) -> torch.Tensor:
             torch.cuda.synchronize(x.device)      # the dropped program's arenas may still be read by kernels in flight
             cache.pop(next(iter(cache)))
         with torch.cuda.device(x.device):
-            bound = TrainBound(lower(module.cfg, B, T, F, prec), x.device)
+            bound = TrainBound(lower(module.cfg, B, T, F, prec, varlen=True) if varlen else lower(module.cfg, B, T, F, prec), x.device)
     cache[key] = bound                               # most recently used last
     bound.use_graph = bool(getattr(module, "use_graph", True)) and not torch.cuda.is_current_stream_capturing()
     sd = dict(module.named_parameters())
     params = [sd[k] for k in bound.prog.keys]
     sync = module.__dict__.get("grad_allreduce", None)          # None | True (default group) | a process group
     with torch.cuda.device(x.device):
+        if varlen:
+            if isinstance(lengths, torch.Tensor):
+                bound.lens.copy_(lengths.to(torch.int32), non_blocking=True)
+            else:
+                bound.lens.copy_(torch.as_tensor(lengths, dtype=torch.int32).pin_memory(), non_blocking=True)
         out = TrainFn.apply(bound, sync, inputs, *params)
         bound.update_bn_buffers(module)
     return out

@@ -887,6 +887,49 @@ int eab_lstm64_train_fwd_prec_f32(const float* x, const float* wcat, const float
 int eab_lstm64_bwd_prec_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, int B, int T, int F,
                             int precision, eab_stream_t stream);
 
+/* Which kernel eab_lstm64_bwd_prec_f32 takes for a problem (host only, launches nothing): the 4-sequence kernel masks its
+ * loads with the out-of-range offset 2^31 of a 32-bit buffer descriptor, so it is admitted only while the gate tensor
+ * (B*F * T * 5 * 64 floats) stays below 2^31 bytes; larger problems take the 16-sequence kernel.  < 0: invalid arguments. */
+#define EAB_LSTM_BWD_FORM_Q       0   /* 4 sequences per workgroup (up to 2048 sequences) */
+#define EAB_LSTM_BWD_FORM_16      1   /* 16 sequences per workgroup, fp32 recurrent products */
+#define EAB_LSTM_BWD_FORM_16_BF16 2   /* 16 sequences per workgroup, bf16 recurrent products */
+int eab_lstm64_bwd_form(int B, int T, int F, int precision);
+
+/* Training with per-utterance lengths: the `_lens` forms of the kernels that sum or recurse across rows.  `lens`: DEVICE
+ * memory, B frame counts, 1 <= lens[b] <= T (eab_time_window.lens); utterance b is its first lens[b] of T frames.  No row of
+ * a frame t >= lens[b] of any operand is read by a sum or a recurrence -- those rows may hold anything, NaN included -- and
+ * lens == NULL is the entry point without the suffix, bit for bit.
+ *   in_stats / in1d / in1d_multi, norm_bwd / norm_bwd_multi: P = T * (positions per frame); statistics, the divisor 1/P and
+ *     the parameter gradients run over the first lens[b] * P / T positions; rows behind them are neither read nor written.
+ *   layernorm64_bwd: rows = [B][T][F]; dg, db sum the rows of valid frames (dx is row-local, written for every row).
+ *   lstm64_bwd: steps t >= lens[b] load zeros (as steps t < 0 do): the carries through the padding stay zero, dgates there are
+ *     written as zeros.  The predicate is per sequence (b, f).
+ *   wgrad_batch: a row (b, t, o) with t >= lens[b], or whose tap reads a frame >= lens[b], reads 0 in both operands and in dbias.
+ *   filter_sum_ld: output frames t >= lens[b] are written as exact zeros by selection.
+ * The convolutions take lens in eab_conv_desc.win: rows of padding frames are neither computed nor stored nor counted, and no
+ * tap gathers a source frame >= lens[b] (the look-ahead taps of a data gradient would read stale rows there). */
+int eab_train_in_stats_lens_f32(const float* x, const float* slope, int B, int P, int C, float eps, const float* gamma,
+                                const float* beta, float* xf, float* mr, const int32_t* lens, int T, eab_stream_t stream);
+int eab_train_in1d_lens_f32(const float* x, const float* slope, int B, int P, int C, float eps, const float* gamma,
+                            const float* beta, float* xf, float* mr, float* y, const int32_t* lens, int T, eab_stream_t stream);
+int eab_train_in1d_multi_lens_f32(const float* x, const float* slope, int B, int P, int C, int xC, float eps, const float* gamma,
+                                  const float* beta, float* xf, float* mr, float* y, const int32_t* lens, int T,
+                                  eab_stream_t stream);
+int eab_train_norm_bwd_lens_f32(const float* dy, const float* x, const float* mr, const float* gamma, const float* beta,
+                                const float* slope, float* sums, const float* acc_in, float* dx, float* dgamma, float* dbeta,
+                                float* dslope, int B, int P, int C, int mode, const int32_t* lens, int T, eab_stream_t stream);
+int eab_train_norm_bwd_multi_lens_f32(const float* dy0, const float* dy1, const float* x, const float* mr, const float* gamma,
+                                      const float* slope, float* sums, const float* acc_in, float* dx, float* dgamma,
+                                      float* dbeta, float* dslope, int B, int P, int xC, const int32_t* lens, int T,
+                                      eab_stream_t stream);
+int eab_layernorm64_bwd_lens_f32(const float* dy, const float* x, const float* mr, const float* g, float* dx, float* dg,
+                                 float* db, long long rows, const int32_t* lens, int B, int T, eab_stream_t stream);
+int eab_lstm64_bwd_lens_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, const int32_t* lens,
+                            int B, int T, int F, int precision, eab_stream_t stream);
+int eab_filter_sum_ld_lens_f32(const float* w, const float* x, float* y, int B, int T, int F, int M, int ld, const int32_t* lens,
+                               eab_stream_t stream);
+int eab_wgrad_batch_lens_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, const int32_t* lens, eab_stream_t stream);
+
 /* Weight gradient on fp32 MFMA:
  *   dw[n][tap*UPT*16 + c] += sum_{b,t,o} dz[b][t][o*ostride+ophase][n] * src[b][t+dt_tap][o*istride+ioff_tap][c]
  * with the forward geometry of eab_conv_desc (plain sources, optional concatenation), tap-major columns,
@@ -899,12 +942,13 @@ int eab_wgrad_f32(const eab_wgrad_desc* d, eab_stream_t stream);
 int eab_wgrad_batchable(const eab_wgrad_desc* descs, int n, int stride_bytes);
 int eab_wgrad_batch_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, eab_stream_t stream);
 
-/* op kinds of the training programs (eab_run_program); field use:
+/* op kinds of the training programs (eab_run_program).  win.lens (per-utterance lengths) is honoured by IN_STATS, NORM_BWD,
+ * LN_BWD, LSTM_BWD, FILTER_SUM and WGRAD through their `_lens` entry points (T: only read then); field use:
  *  GATHER       p = {flat, ia, ib, out}                 i = {n_lo, n_hi}
- *  IN_STATS     p = {x, slope, gamma, beta, xf, mr, y}  i = {B, P, C, xC}      f = {eps}     (y != NULL: eab_train_in1d_f32; xC > 0: _multi_)
+ *  IN_STATS     p = {x, slope, gamma, beta, xf, mr, y}  i = {B, P, C, xC, T}   f = {eps}     (y != NULL: eab_train_in1d_f32; xC > 0: _multi_)
  *  IN_FINALIZE  as before, plus p[7], p[8] = mr0, mr1
  *  TR_NORM_ACT  p = {x, xf, slope, add, y}              i = {B, P, C, mode}
- *  NORM_BWD     p = {dy, x, mr, gamma, beta, slope, sums, acc_in, dx, dgamma, dbeta, dslope}   i = {B, P, C, mode, xC}
+ *  NORM_BWD     p = {dy, x, mr, gamma, beta, slope, sums, acc_in, dx, dgamma, dbeta, dslope}   i = {B, P, C, mode, xC, T}
  *               (xC > 0: eab_train_norm_bwd_multi_f32 with p[4] = dy1 instead of beta)
  *  GLU_BWD      p = {dy, dump, dz}                      i = {rows_lo, rows_hi, N}
  *  GATE_FWD     p = {a, r, z}        GATE_BWD p = {dz, a, r, da, dr}       i = {n_lo, n_hi}
@@ -912,7 +956,7 @@ int eab_wgrad_batch_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, ea
  *  COLSUM       p = {x, out}                            i = {rows_lo, rows_hi, N}
  *  FILTER_SUM   p = {w, x, y}        FS_BWD   p = {dout, x, dw}            i = {B, T, F, M, ld}
  *  LN_FWD       p = {x, g, b, y, mr} f = {eps}          i = {rows_lo, rows_hi}
- *  LN_BWD       p = {dy, x, mr, g, dx, dg, db}          i = {rows_lo, rows_hi}
+ *  LN_BWD       p = {dy, x, mr, g, dx, dg, db}          i = {rows_lo, rows_hi, B, T}
  *  LSTM_TRAIN   p = {x, wcat, bias, h_out, gates}       i = {B, T, F}
  *  LSTM_BWD     p = {gates, dh_out, wcat, dgates}       i = {B, T, F}
  *  GAG_CRM_BWD  p = {pre, g, dplanar, dpre_out, acc_in, dg, dr, di, dpre}   i = {B, T, F, ld, lin_ld, act}
