@@ -99,6 +99,10 @@ _SIGS = {
                             + [C.c_void_p] * 4),
     "eab_si_sdr_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_int, C.c_double, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "eab_sdr_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p,
+                              C.c_int] + [C.c_void_p] * 3),
+    "eab_sdr_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_longlong, C.c_void_p]),
     "eab_mrstft_workspace_bytes": (C.c_longlong, [C.c_void_p] + [C.c_int] * 4),
     "eab_mrstft_loss_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
                             + [C.c_double] * 3 + [C.c_void_p, C.c_longlong] + [C.c_void_p] * 4),

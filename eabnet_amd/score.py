@@ -8,7 +8,11 @@ table -- si_sdr, si_sir, si_sar, si_sdr_mix, loss per file -- which it copies to
 
 ``intelligibility`` is csrc/stoi.hip behind tensor arguments: STOI and ESTOI per utterance at 10 kHz (the two remaining
 closed-form metrics of cal_single_metrics), ``stoi`` the same with the host library's argument order, and
-``Scorer(..., intelligibility=True)`` adds them as two more columns."""
+``Scorer(..., intelligibility=True)`` adds them as two more columns.
+
+``sdr`` is csrc/sdr.hip behind tensor arguments: the SDR of BSS-eval -- the estimate projected on 512 shifts of the clean wave, the
+distortion number reported next to PESQ and STOI, which does not ask for alignment to the sample -- and
+``Scorer(..., distortion=True)`` adds it for the enhanced and the unprocessed wave as the columns ``sdr`` and ``sdr_mix``."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -23,13 +27,15 @@ from .enhance import MODEL_RATE, Batch, Enhancer
 
 METRICS = ("si_sdr", "si_sir", "si_sar", "si_sdr_mix", "loss")
 INTELLIGIBILITY_METRICS = ("stoi", "estoi")
+DISTORTION_METRICS = ("sdr", "sdr_mix")
+SDR_MAX_TAPS = 512                            # SDR_MAX_TAPS of csrc/sdr.hip
 STOI_RATE = 10000                             # the rate of the definition: other rates are resampled to it first
 
 
-def _rows(t: torch.Tensor) -> torch.Tensor:
+def _rows(t: torch.Tensor, fn: str = "energy_ratios") -> torch.Tensor:
     """a signal of the scores as fp32 rows the kernels read (the losses refuse other dtypes; the scores cast them)"""
     if not t.is_cuda:
-        raise _lib.EabError("energy_ratios needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
+        raise _lib.EabError(f"{fn} needs CUDA (ROCm) tensors; there is no CPU fallback by design.")
     if t.dtype != torch.float32:
         t = t.to(torch.float32)
     return _rw.in_place(t)
@@ -152,6 +158,63 @@ def intelligibility(est: torch.Tensor, clean: torch.Tensor, lengths=None, sample
     return _stoi_rows(est, clean, cols, taps)
 
 
+def check_sdr_filter(filter_length, load_diag):
+    """(filter_length, load_diag) of ``sdr`` and ``sdr_loss`` checked, or ValueError"""
+    if isinstance(filter_length, bool) or not isinstance(filter_length, int) or not 1 <= filter_length <= SDR_MAX_TAPS:
+        raise ValueError(f"filter_length must be an integer in [1, {SDR_MAX_TAPS}], got {filter_length!r}")
+    if isinstance(load_diag, bool) or not (isinstance(load_diag, (int, float)) and 0.0 <= float(load_diag) < float("inf")):
+        raise ValueError(f"load_diag must be a finite number >= 0, got {load_diag!r}")
+    return filter_length, float(load_diag)
+
+
+def _sdr_rows(est: torch.Tensor, clean: torch.Tensor, lens: torch.Tensor, K: int, load_diag: float, eps: float, filters: bool):
+    """the two launches of csrc/sdr.hip on fp32 rows and (B, 2) device lengths: out (B, 6) float64 [sdr_dB, tgt, ee, loss, a, c]
+    and the filters (B, K) float64 (None unless asked for)"""
+    lib = _lib.load()
+    B = est.shape[0]
+    with torch.cuda.device(est.device):
+        spans = _rw.spans(max(est.shape[1], clean.shape[1]))
+        partial = torch.empty((B, spans, 2 * K + 1), dtype=torch.float64, device=est.device)
+        out = torch.empty((B, 6), dtype=torch.float64, device=est.device)
+        h = torch.empty((B, K), dtype=torch.float64, device=est.device) if filters else None
+        _lib.check(lib.eab_sdr_f32(*_rw.row_args(B, est, clean), lens.data_ptr(), B, K, load_diag, eps, partial.data_ptr(), spans,
+                                   out.data_ptr(), h.data_ptr() if filters else None, _rw.stream()), "eab_sdr_f32")
+    return out, h
+
+
+def sdr(est: torch.Tensor, clean: torch.Tensor, lengths=None, filter_length: int = 512, load_diag: float = 0.0, filters: bool = False):
+    """The SDR of BSS-eval of B utterances: (B, Le), (B, Ls) CUDA fp32 tensors -> a (B,) float64 device tensor in dB
+    (``filters=True``: ``(sdr, h)`` with the (B, filter_length) float64 projection filters).  With K = filter_length and each
+    signal zero from its own length up to the longer of the two (never read there):
+
+        r[k] = sum_n s[n] s[n+k]   c[k] = sum_n s[n] e[n+k]   R = Toeplitz(r) + load_diag r[0] I   h = R^-1 c
+        sdr = 10 log10( c.h / (sum_n e[n]^2 - c.h) )                                                  k = 0 .. K-1
+
+    c.h is the energy of the estimate's projection on the clean wave shifted by 0 .. K-1 samples: the single-source SDR of
+    mir_eval / fast_bss_eval in exact arithmetic (equality with those libraries is NOT verified; DESIGN §4.25 is the contract).
+    It does not ask for alignment to the sample: a delayed or lightly filtered copy of the clean wave scores by its noise alone.
+    K = 1 is the ``si_sdr`` of ``energy_ratios``.  Rows may be strided views whose last dimension is contiguous and are read in
+    place; lengths: an optional pair of (B,) sample counts for (est, clean), host or device, as in ``intelligibility``.  A silent
+    clean row, a clean row of fewer than K samples and a row whose recursion meets a prediction error <= 0 give NaN in their
+    own row only.  Correlations, the Levinson recursion and the ratio in fp64 in a fixed order: a row has the same bits alone,
+    in any batch and in a second call."""
+    for name, t in (("est", est), ("clean", clean)):
+        if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be a (B, L) tensor, got {tuple(t.shape)}")
+    B = est.shape[0]
+    if clean.shape[0] != B:
+        raise ValueError(f"est and clean must hold the same number of rows, got {B} and {clean.shape[0]}")
+    K, load_diag = check_sdr_filter(filter_length, load_diag)
+    cols = _rw.check_lens(lengths, B, (est.shape[1], clean.shape[1]), "pair (est, clean)")
+    est, clean = _rows(est, "sdr"), _rows(clean, "sdr")
+    if est.device != clean.device:
+        raise ValueError("est and clean must be on one device")
+    with torch.cuda.device(est.device):
+        lens = _rw.device_lens(cols, B, est.device)
+    out, h = _sdr_rows(est, clean, lens, K, load_diag, 0.0, bool(filters))
+    return (out[:, 0], h) if filters else out[:, 0]
+
+
 def stoi(clean, est, fs_sig: int, extended: bool = False) -> float:
     """``stoi(clean, est, fs_sig, extended)`` with the host library's argument order, as test.py calls it: 1-D tensors or arrays
     -> a Python float, STOI or (``extended=True``) ESTOI by ``intelligibility`` (whose definition, not that library's output, is
@@ -173,9 +236,11 @@ class _ScorerType(type):
     """``Scorer(..., intelligibility=True)``: the switch is a keyword of the class call, not of ``__init__``, whose parameter list
     is pinned together with the other tools' (tests/test_resample_ref.py::test_defaults_of_the_tools_are_unchanged)."""
 
-    def __call__(cls, *args, intelligibility: bool = False, **kw):
+    def __call__(cls, *args, intelligibility: bool = False, distortion: bool = False, **kw):
         self = super().__call__(*args, **kw)
         self.intelligibility = bool(intelligibility)
+        if distortion:                        # (off: the instance keeps the class's False and nothing else changes)
+            self.distortion = True
         return self
 
 
@@ -197,9 +262,14 @@ class Scorer(Enhancer, metaclass=_ScorerType):
     ``intelligibility=True`` adds the keys ``stoi`` and ``estoi`` (a (N, 7) table): per batch, on the same stream, the enhanced
     waves and the clean buffer are resampled from 16 kHz to 10 kHz and scored by ``intelligibility`` with the lengths
     (hop * (T_b - 1), L_b).  The default changes nothing: not the keys, the table, the launches or the bits.  (The attribute
-    ``scorer.intelligibility`` may also be set between calls.)"""
+    ``scorer.intelligibility`` may also be set between calls.)
+
+    ``distortion=True`` adds the keys ``sdr`` and ``sdr_mix`` after those: per batch, on the same stream, ``sdr`` (the SDR of
+    BSS-eval with 512 taps) of the enhanced waves against the clean buffer with the lengths (hop * (T_b - 1), L_b), and of
+    noisy[ref_mic] against it with (L_b, L_b).  A file of fewer than 512 samples gives NaN in these two.  Off, nothing changes."""
 
     intelligibility = False
+    distortion = False
 
     def __init__(self, model, max_batch: int = 16, fft_num: int = 320, hop: int = 160, window: Optional[torch.Tensor] = None,
                  length_buckets="auto", ref_mic: int = 0, sample_rate: int = 16000, mic_order=None):
@@ -230,6 +300,9 @@ class Scorer(Enhancer, metaclass=_ScorerType):
         ratios = energy_ratios(wav, cbuf[:, 0], noisy[:, self.ref_mic], lengths=([hop * (t - 1) for t in counts], samples, samples))
         if self.intelligibility:              # (before the events below: it reads the staged clean waves too)
             intel = intelligibility(wav, cbuf[:, 0], lengths=([hop * (t - 1) for t in counts], samples), sample_rate=MODEL_RATE)
+        if self.distortion:
+            dist = sdr(wav, cbuf[:, 0], lengths=([hop * (t - 1) for t in counts], samples))
+            dist_mix = sdr(noisy[:, self.ref_mic], cbuf[:, 0], lengths=(samples, samples))
         for e in (ev, cev):
             if e is not None:                 # the staged noisy and clean waves have no reader after this point
                 e.record(torch.cuda.current_stream(device))
@@ -239,13 +312,17 @@ class Scorer(Enhancer, metaclass=_ScorerType):
         rows[:, 4].copy_(loss[:n])
         if self.intelligibility:
             rows[:, 5:7].copy_(intel[:n])
+        if self.distortion:
+            col = len(self.metrics) - 2
+            rows[:, col].copy_(dist[:n])
+            rows[:, col + 1].copy_(dist_mix[:n])
         self._filled += n
         self._tick("score")
 
     @property
     def metrics(self) -> Tuple[str, ...]:
         """the keys of the scores, in the order of the table's columns"""
-        return METRICS + (INTELLIGIBILITY_METRICS if self.intelligibility else ())
+        return METRICS + (INTELLIGIBILITY_METRICS if self.intelligibility else ()) + (DISTORTION_METRICS if self.distortion else ())
 
     @torch.no_grad()
     def __call__(self, noisy_waves: Sequence[torch.Tensor], clean_waves: Sequence[torch.Tensor], return_waves: bool = False):

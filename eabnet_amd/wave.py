@@ -13,7 +13,11 @@ time-frequency resolutions, csrc/spec_loss.hip -- added the same way: ``loss = l
 
 ``stoi_loss`` trains for the two intelligibility scores ``Scorer(model, intelligibility=True)`` reports: minus a weighted sum of
 STOI and ESTOI, the value by the launches of ``intelligibility`` and the gradient by three more on the workspace they leave
-(csrc/stoi_bwd.hip); at 16 kHz it chains through the differentiable ``resample``."""
+(csrc/stoi_bwd.hip); at 16 kHz it chains through the differentiable ``resample``.
+
+``sdr_loss`` is ``si_sdr_loss`` with a filter of up to 512 taps between the clean wave and the estimate -- minus the SDR of
+BSS-eval that ``sdr`` reports (csrc/sdr.hip) -- for targets that are a delayed or lightly filtered copy of what
+the array should deliver, where the one-tap loss and its gradient say nothing."""
 from __future__ import annotations
 
 import ctypes as C
@@ -24,7 +28,7 @@ import torch
 from . import _lib
 from . import _rows as _rw
 from . import model as _m
-from .score import STOI_RATE
+from .score import STOI_RATE, _sdr_rows, check_sdr_filter
 
 REDUCTIONS = ("mean", "sum", "none")
 
@@ -85,6 +89,70 @@ def si_sdr_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, eps: float
     with torch.cuda.device(est.device):
         lens = _rw.device_lens(cols, B, est.device)
     return _SiSdrLoss.apply(est_rows, clean_rows, lens, float(eps), reduction)
+
+
+class _SdrLoss(torch.autograd.Function):
+    """value: eab_sdr_f32 leaves (sdr, tgt, ee, loss_b, a_b, c_b) and the filter h per utterance in fp64; backward:
+    eab_sdr_loss_bwd_f32 writes g_b (a_b e + c_b h * s) from grad_output on the device"""
+
+    @staticmethod
+    def forward(ctx, est, clean, lens, K, load_diag, eps, reduction):
+        B = est.shape[0]
+        e, s = est.detach(), clean
+        out, h = _sdr_rows(e, s, lens, K, load_diag, eps, True)
+        with torch.cuda.device(e.device):
+            loss = out[:, 3]
+            if reduction != "none":
+                loss = loss.sum()
+                if reduction == "mean":
+                    loss = loss / B
+            loss = loss.to(torch.float32)
+        ctx.save_for_backward(e, s, lens, out, h)
+        ctx.cfg = (K, reduction)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        e, s, lens, coef, h = ctx.saved_tensors
+        K, reduction = ctx.cfg
+        lib = _lib.load()
+        B, L = e.shape
+        g, gstride, scale = _rw.grad_row(g, B, reduction)
+        with torch.cuda.device(e.device):
+            grad = torch.empty((B, L), dtype=torch.float32, device=e.device)
+            _lib.check(lib.eab_sdr_loss_bwd_f32(*_rw.row_args(B, e, s), lens.data_ptr(), B, K, coef.data_ptr(), h.data_ptr(), g.data_ptr(),
+                                                gstride, scale, grad.data_ptr(), L, _rw.stream()), "eab_sdr_loss_bwd_f32")
+        return grad, None, None, None, None, None, None
+
+
+def sdr_loss(est: torch.Tensor, clean: torch.Tensor, lengths=None, filter_length: int = 512, load_diag: float = 0.0, eps: float = 0.0,
+             reduction: str = "mean") -> torch.Tensor:
+    """Negative SDR of BSS-eval in dB of B utterances, differentiable with respect to ``est``: est (B, Le), clean (B, Ls) or
+    (B, 1, Ls), CUDA fp32 -> an fp32 scalar (``reduction`` "mean" or "sum") or (B,) ("none").  With K = filter_length, r, c, R and
+    h as in ``sdr``, tgt = c.h and res = max(|e|^2 - tgt, 0):
+
+        loss_b = -10 log10( (tgt + eps) / (res + eps) )
+        d loss_b / d e[n] = a_b e[n] + c_b (h * s)[n],   a_b = 2 k10 / (res + eps),  c_b = -2 k10 [1 / (tgt + eps) + 1 / (res + eps)]
+
+    With ``eps=0`` loss_b is minus ``sdr`` on the same rows, and with ``filter_length=1`` every formula is that of
+    ``si_sdr_loss``.  The filter h * s, the sums and a_b e + c_b (h * s) are fp64, rounded to fp32 once: e and its projection
+    cancel at high SDR.  lengths, strided rows, the zero convention past a length and the exactly zero gradient from est's length
+    to the row's end: as ``si_sdr_loss``.  A silent clean row, a clean row of fewer than K samples and a row whose recursion
+    meets a prediction error <= 0 give NaN in their own value and their own gradient row only.  Every sum has one fixed order:
+    an utterance has the same bits alone, in any batch and in a second call, value and gradient.  No double backward.  No
+    operator fallback: CPU tensors, other dtypes and a ``clean`` that requires grad raise."""
+    if reduction not in REDUCTIONS:
+        raise ValueError(f"reduction must be one of {REDUCTIONS}, got {reduction!r}")
+    if not (isinstance(eps, (int, float)) and 0.0 <= float(eps) < float("inf")):
+        raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
+    K, load_diag = check_sdr_filter(filter_length, load_diag)
+    clean, B = _rw.check_waves("sdr_loss", est, clean)
+    cols = _rw.check_lens(lengths, B, (est.shape[1], clean.shape[1]))
+    est_rows, clean_rows = _rw.device_rows("sdr_loss", est, clean)
+    with torch.cuda.device(est.device):
+        lens = _rw.device_lens(cols, B, est.device)
+    return _SdrLoss.apply(est_rows, clean_rows, lens, K, load_diag, float(eps), reduction)
 
 
 MR_RESOLUTIONS = ((1024, 120, 600), (2048, 240, 1200), (512, 50, 240))

@@ -243,6 +243,42 @@ int eab_si_sdr_loss_bwd_f32(const float* est, long long est_stride, int est_cap,
                             int grad_out_stride, double scale, float* grad, long long grad_stride, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
+ * BSS-eval SDR per utterance of a padded batch, value and gradient (csrc/sdr.hip; definition: DESIGN.md §4.25): the estimate
+ * projected on the K = filter_length shifts of the clean wave, the single-source SDR of mir_eval / fast_bss_eval in exact
+ * arithmetic (equality with those libraries is not verified).  Only entry points are added: EAB_ABI_VERSION stays 10.
+ *
+ *   est, clean, lens: as eab_si_sdr_loss_f32 (lens DEVICE int32 [B][2], clamped; nothing is read at or past a length)
+ * With N the longer of the two signals, k10 = 10 / ln 10 and k = 0 .. K-1:
+ *   r[k] = sum_n s[n] s[n+k]    c[k] = sum_n s[n] e[n+k]    ee = sum_n e[n]^2
+ *   R = Toeplitz(r) + load_diag r[0] I     h = R^-1 c     tgt = c . h     res = max(ee - tgt, 0)
+ *   sdr_b = 10 log10(tgt / res)            loss_b = -k10 [ ln(tgt + eps) - ln(res + eps) ]
+ *   d loss_b / d e[n] = a_b e[n] + c_b p[n] for n < lens[b][0],   p[n] = sum_k h[k] s[n-k],
+ *   a_b = 2 k10 / (res + eps),   c_b = -2 k10 [ 1 / (tgt + eps) + 1 / (res + eps) ].     K = 1: the formulas of eab_si_sdr_loss_f32.
+ * eab_sdr_f32 (two launches: correlations per span of 4096 samples, then one wave per utterance adds the spans in index order and
+ * runs the symmetric Levinson recursion with a right-hand side, all in fp64):
+ *   filter_length in [1, 512];  load_diag >= 0 and eps >= 0, finite
+ *   partial device scratch of B * partial_spans * (2 filter_length + 1) doubles, partial_spans >= ceil(max(cap) / 4096)
+ *   out     device double [B][6]: sdr_b (dB), tgt, ee, loss_b, a_b, c_b
+ *   h       device double [B][filter_length], or NULL when the filters are not wanted
+ *   A row whose r[0] is not positive, whose recursion meets a prediction error <= 0, or whose clean wave has fewer than
+ *   filter_length samples is not scored: NaN in ITS row of out and h, no other row touched.
+ * eab_sdr_loss_bwd_f32 (one launch): grad[b][n] = grad_out[b * grad_out_stride] * scale * (a_b e[n] + c_b p[n]) for
+ * n < lens[b][0] and exactly 0 from there to est_cap; the taps, the sums and the combination in fp64, rounded to fp32 once.
+ *   coef, h the `out` and the `h` of the forward call on the same rows, lens and filter_length
+ *   grad_out, scale, grad, grad_stride: as eab_si_sdr_loss_bwd_f32
+ * EAB_EINVAL before any launch for a NULL pointer (but h of eab_sdr_f32), rows eab_si_sdr_loss_f32 refuses, filter_length outside
+ * [1, 512], a negative or non-finite load_diag or eps, and partial_spans too small.  Every sum has one fixed order, no atomics:
+ * an utterance has the same bits alone, in any batch and in a second call, whatever the strides and alignments.
+ * ------------------------------------------------------------------------ */
+int eab_sdr_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride, int clean_cap,
+                const int32_t* lens, int B, int filter_length, double load_diag, double eps, double* partial, int partial_spans,
+                double* out, double* h, eab_stream_t stream);
+int eab_sdr_loss_bwd_f32(const float* est, long long est_stride, int est_cap, const float* clean, long long clean_stride,
+                         int clean_cap, const int32_t* lens, int B, int filter_length, const double* coef, const double* h,
+                         const float* grad_out, int grad_out_stride, double scale, float* grad, long long grad_stride,
+                         eab_stream_t stream);
+
+/* --------------------------------------------------------------------------
  * Multi-resolution STFT loss on the waveform, value and gradient (csrc/spec_loss.hip; definition and deviations: DESIGN.md §4.21).
  * Only entry points are added: EAB_ABI_VERSION stays 10.
  *
