@@ -95,6 +95,8 @@ _SIGS = {
     "eab_istft_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
     "eab_istft_lens_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "eab_istft_bwd_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "eab_istft_lin_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
+    "eab_istft_lin_bwd_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
     "eab_si_sdr_loss_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_int]
                             + [C.c_void_p] * 4),
     "eab_si_sdr_loss_bwd_f32": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int] * 2 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

@@ -70,7 +70,7 @@ def _padded_len(longest: int, frames: int, hop: int) -> int:
     return L if L >= longest else longest
 
 
-class Enhancer:
+class Enhancer(metaclass=_m._DecompressType):
     """``enh = Enhancer(model); waves_out = enh(waves)``: a list of (M, L_i) waves, host or device, any mix of lengths ->
     the list of enhanced (hop * (T_i - 1),) waves on the model's device, in input order (T_i = 1 + L_i // hop frames, what
     the one-at-a-time chain ``stft_compress -> model -> istft`` returns for each file).
@@ -99,8 +99,15 @@ class Enhancer:
     ``output_rate``: None returns 16 kHz waves (enhance.py:63), an int or "input" resamples each batch's enhanced waves, with
     their lengths, before they are sliced out.
 
+    ``Enhancer(..., decompress=True)`` (a bool, default False: the reference's waves; a keyword of the class call, see
+    ``model._DecompressType``) is passed to every ``istft`` call: True undoes the front end's sqrt compression inside the
+    back-end kernel, so each wave is an estimate of the signal in the clean files rather than of one whose spectrum has
+    square-rooted magnitudes.  (The attribute ``enhancer.decompress`` may also be set between calls.)
+
     ``last_plan`` describes the last call: its batches (files, cap, batch size, dummies, frames), the dummy count, and the
     valid frames against the frames padded up to each batch's longest member and up to its cap."""
+
+    decompress = False
 
     def __init__(self, model, max_batch: int = 16, fft_num: int = 320, hop: int = 160, window: Optional[torch.Tensor] = None,
                  length_buckets="auto", sample_rate: int = MODEL_RATE, mic_order=None, output_rate=None):
@@ -229,7 +236,7 @@ class Enhancer:
             if ev is not None:
                 ev.record(torch.cuda.current_stream(device))
             est = self._model(spec, None)
-            wav = _m.istft(est, fft, hop, self.window)
+            wav = _m.istft(est, fft, hop, self.window, decompress=self.decompress)
             self._batch_done(batch, buf, ev, est, wav, [buf.shape[2]], [est.shape[2]], False, device)
             return [self._output(wav, None)[0]]
         B, T_max = batch.batch_size, frames[batch.indices[0]]
@@ -253,7 +260,7 @@ class Enhancer:
         self._tick("stft")
         est = self._model(spec[:, :T_max], counts)
         self._tick("model")
-        wav = _m.istft(est, fft, hop, self.window, lengths=counts)
+        wav = _m.istft(est, fft, hop, self.window, lengths=counts, decompress=self.decompress)
         self._tick("istft")
         res = self._output(wav, [hop * (c - 1) for c in counts])
         out = [res[k, :self._out_len(hop * (counts[k] - 1))].clone() for k in range(len(mine))]

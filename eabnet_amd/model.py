@@ -978,7 +978,22 @@ class TwoStageStream:
         return {"esti0_stft": esti0, "esti1_stft_list": lst, "esti_stft": lst[-1].permute(0, 1, 3, 2)}
 
 
-class StreamingEnhancer:
+class _DecompressType(type):
+    """``Enhancer(..., decompress=True)``, ``Scorer(...)``, ``StreamingEnhancer(...)``: the switch is a keyword of the class call
+    (what ``inspect.signature`` of the class shows), not of ``__init__``, whose parameter lists are pinned
+    (tests/test_resample_ref.py::test_defaults_of_the_tools_are_unchanged).  It must be a bool; the instance attribute
+    ``decompress`` is what the ``istft`` calls of the tool are given.  False leaves the instance as ``__init__`` made it."""
+
+    def __call__(cls, *args, decompress: bool = False, **kw):
+        if not isinstance(decompress, bool):
+            raise TypeError(f"decompress must be a bool, got {type(decompress).__name__}")
+        self = super().__call__(*args, **kw)
+        if decompress:
+            self.decompress = True
+        return self
+
+
+class StreamingEnhancer(metaclass=_DecompressType):
     """enhance.py:45-62 as a real-time loop on the device: ``push`` takes the next ``chunk`` hops of
     multichannel samples (B, M, chunk*hop) and returns the enhanced samples that became final.
 
@@ -992,7 +1007,13 @@ class StreamingEnhancer:
     call; a ``StreamResampler`` turns them into ``sr`` samples (bit for bit those of the offline ``resample``), which queue up
     until a whole chunk*hop block is there for the push logic above.  The output (at ``sr``) trails the input by the filter's
     half-width more -- 19 samples at 48 kHz, 0.4 ms -- so the first call returns one block less and ``last=True`` returns the
-    rest.  ``mic_order``: the microphones of the pushed samples in the model's order."""
+    rest.  ``mic_order``: the microphones of the pushed samples in the model's order.
+
+    ``StreamingEnhancer(..., decompress=True)`` (a bool, default False: the reference's wave) is passed to the ``istft`` call
+    of every push: True undoes the front end's sqrt compression, so the streamed wave is an estimate of the signal in the
+    clean files, bit for bit the offline chain with ``istft(decompress=True)``."""
+
+    decompress = False
 
     def __init__(self, model, B: int, seconds: float, chunk: int = 1, sr: int = 16000, fft_num: int = 320, hop: int = 160,
                  endless: bool = False, sample_rate: Optional[int] = None, mic_order=None):
@@ -1082,7 +1103,7 @@ class StreamingEnhancer:
         self._spec_prev = est[:, :, -1:].clone()
         if seq.shape[2] < 2:
             return samples.new_zeros((B, 0))
-        return istft(seq, self.fft, self.hop, self.window)
+        return istft(seq, self.fft, self.hop, self.window, decompress=self.decompress)
 
 
 def make_eabnet_with_postnet(args) -> EaBNetWithPostNet:
@@ -1344,58 +1365,85 @@ def _check_nola(window: torch.Tensor, fft_num: int, hop: int, T: int, key_window
                            f"window / hop: fft_num={fft_num}, win_shift={hop})")
 
 
+def _istft_launch(lib, x: torch.Tensor, window: torch.Tensor, tw: torch.Tensor, wav: torch.Tensor, lens, fft_num: int, hop: int,
+                  decompress: bool) -> None:
+    """the one forward launch of ``istft``, with and without autograd: fp32 contiguous x (B, 2, T, F) -> wav (B, hop (T-1));
+    lens: the device frame counts or None"""
+    B, _, T, _ = x.shape
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if decompress:
+        _lib.check(lib.eab_istft_lin_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(),
+                                         None if lens is None else lens.data_ptr(), B, T, fft_num, hop, stream), "eab_istft_lin_f32")
+    elif lens is not None:
+        _lib.check(lib.eab_istft_lens_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(), lens.data_ptr(),
+                                          B, T, fft_num, hop, stream), "eab_istft_lens_f32")
+    else:
+        _lib.check(lib.eab_istft_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(), B, T, fft_num, hop, stream),
+                   "eab_istft_f32")
+
+
 class _Istft(torch.autograd.Function):
     """``istft`` on an input that requires grad: the forward is the launch ``istft`` makes for any other input (the same
-    values), the backward the adjoint kernel eab_istft_bwd_f32 on the same window and, where given, the same lengths."""
+    values), the backward the adjoint kernel eab_istft_bwd_f32 on the same window and, where given, the same lengths.  With
+    ``decompress`` the node keeps the fp32 spectrum and its backward is eab_istft_lin_bwd_f32 at that spectrum."""
 
     @staticmethod
-    def forward(ctx, esti: torch.Tensor, window: torch.Tensor, lengths, fft_num: int, hop: int) -> torch.Tensor:
+    def forward(ctx, esti: torch.Tensor, window: torch.Tensor, lengths, fft_num: int, hop: int, decompress: bool) -> torch.Tensor:
         lib = _lib.load()
         B, _, T, _ = esti.shape
         x = esti.detach().to(torch.float32).contiguous()
         wav = torch.empty((B, hop * (T - 1)), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             tw = _twiddle(fft_num, x.device)
-            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
             lens = None if lengths is None else _device_lengths(lengths, x.device)
-            if lens is not None:
-                _lib.check(lib.eab_istft_lens_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(), lens.data_ptr(),
-                                                  B, T, fft_num, hop, stream), "eab_istft_lens_f32")
-            else:
-                _lib.check(lib.eab_istft_f32(x.data_ptr(), window.data_ptr(), tw.data_ptr(), wav.data_ptr(), B, T, fft_num, hop,
-                                             stream), "eab_istft_f32")
-        ctx.save_for_backward(window, tw, *(() if lens is None else (lens,)))
-        ctx.geom = (B, T, fft_num, hop, esti.dtype)
+            _istft_launch(lib, x, window, tw, wav, lens, fft_num, hop, decompress)
+        ctx.save_for_backward(window, tw, *((x,) if decompress else ()), *(() if lens is None else (lens,)))
+        ctx.geom = (B, T, fft_num, hop, esti.dtype, decompress)
         return wav
 
     @staticmethod
     def backward(ctx, dwav):
         window, tw, *rest = ctx.saved_tensors
-        B, T, fft_num, hop, dtype = ctx.geom
+        B, T, fft_num, hop, dtype, decompress = ctx.geom
+        spec = rest.pop(0) if decompress else None
         lib = _lib.load()
         g = dwav.detach().to(torch.float32).contiguous()
         dspec = torch.empty((B, 2, T, fft_num // 2 + 1), dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
-            _lib.check(lib.eab_istft_bwd_f32(g.data_ptr(), window.data_ptr(), tw.data_ptr(), dspec.data_ptr(),
-                                             rest[0].data_ptr() if rest else None, B, T, fft_num, hop,
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_istft_bwd_f32")
-        return dspec.to(dtype), None, None, None, None
+            lens = rest[0].data_ptr() if rest else None
+            stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+            if decompress:
+                _lib.check(lib.eab_istft_lin_bwd_f32(g.data_ptr(), spec.data_ptr(), window.data_ptr(), tw.data_ptr(), dspec.data_ptr(),
+                                                     lens, B, T, fft_num, hop, stream), "eab_istft_lin_bwd_f32")
+            else:
+                _lib.check(lib.eab_istft_bwd_f32(g.data_ptr(), window.data_ptr(), tw.data_ptr(), dspec.data_ptr(), lens, B, T, fft_num,
+                                                 hop, stream), "eab_istft_bwd_f32")
+        return dspec.to(dtype), None, None, None, None, None
 
 
-def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.Tensor, lengths=None) -> torch.Tensor:
+def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.Tensor, lengths=None,
+          decompress: bool = False) -> torch.Tensor:
     """The reference's back end (enhance.py:59-62, test.py:189-191, train_distributed.py:128-130)
     ``torch.istft(view_as_complex(esti.permute(0,3,2,1)), fft_num, win_shift, win_size, hann)`` in one
     HIP kernel: (B, 2, T, F) -> (B, win_shift*(T-1)).  Like the reference it inverts the estimate as
-    it is (compressed domain).
+    it is (compressed domain) unless ``decompress`` is set.
 
     lengths: optional (B,) frame counts, 2 <= len <= T (a sequence or an integer tensor, host or device): utterance b is
     esti_stft[b, :, :len[b]], later frames are never read.  Its first win_shift*(len[b]-1) samples are those of a call on
     that utterance alone, bit for bit (the envelope counts its own frames only); the samples after them are zeros.  The
     window-overlap condition is checked for the shortest and the longest host length (a device tensor: for T).
 
+    decompress (a bool; default False = the reference, today's launch and bits): True undoes the sqrt compression of
+    ``stft_compress`` / ``prepare_data`` inside the same kernel -- every bin X is inverted as X |X| (eab_istft_lin_f32;
+    DESIGN.md §4.26) -- so the wave is an estimate of the signal in the clean files, the target the waveform losses and the
+    scores compare it with, not of a signal whose spectrum has square-rooted magnitudes.
+
     Differentiable: with grad enabled and ``esti_stft.requires_grad`` the same launch runs inside an autograd node whose
-    backward is the adjoint kernel (eab_istft_bwd_f32), so a loss on the wave -- ``si_sdr_loss`` -- trains
-    the network.  The values are those of the call without grad, bit for bit; the gradient has the input's dtype."""
+    backward is the adjoint kernel (eab_istft_bwd_f32; with ``decompress`` eab_istft_lin_bwd_f32 at the
+    saved fp32 spectrum), so a loss on the wave -- ``si_sdr_loss`` -- trains the network.  The values are those of the call
+    without grad, bit for bit; the gradient has the input's dtype."""
+    if not isinstance(decompress, bool):
+        raise TypeError(f"decompress must be a bool, got {type(decompress).__name__}")
     if lengths is not None:
         if esti_stft.ndim != 4:
             raise ValueError(f"expected (B,2,T,{fft_num // 2 + 1}), got {tuple(esti_stft.shape)}")
@@ -1420,21 +1468,14 @@ def istft(esti_stft: torch.Tensor, fft_num: int, win_shift: int, window: torch.T
     for n in ((T,) if lengths is None or isinstance(lengths, torch.Tensor) else sorted({min(lengths), max(lengths)})):
         _check_nola(window, fft_num, win_shift, n, key_window=given)
     if torch.is_grad_enabled() and esti_stft.requires_grad:
-        # training on the waveform: the same launch, with eab_istft_bwd_f32 as its backward
-        return _Istft.apply(esti_stft, _device_window(window, esti_stft.device), lengths, fft_num, win_shift)
+        # training on the waveform: the same launch, with the adjoint kernel as its backward
+        return _Istft.apply(esti_stft, _device_window(window, esti_stft.device), lengths, fft_num, win_shift, decompress)
     x = esti_stft.detach().to(torch.float32).contiguous()
     window = _device_window(window, x.device)
     wav = torch.empty((B, win_shift * (T - 1)), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        if lengths is not None:
-            lens = _device_lengths(lengths, x.device)
-            _lib.check(lib.eab_istft_lens_f32(x.data_ptr(), window.data_ptr(), _twiddle(fft_num, x.device).data_ptr(),
-                                              wav.data_ptr(), lens.data_ptr(), B, T, fft_num, win_shift,
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_istft_lens_f32")
-            return wav
-        _lib.check(lib.eab_istft_f32(x.data_ptr(), window.data_ptr(), _twiddle(fft_num, x.device).data_ptr(),
-                                     wav.data_ptr(), B, T, fft_num, win_shift,
-                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)), "eab_istft_f32")
+        lens = None if lengths is None else _device_lengths(lengths, x.device)
+        _istft_launch(lib, x, window, _twiddle(fft_num, x.device), wav, lens, fft_num, win_shift, decompress)
     return wav
 
 

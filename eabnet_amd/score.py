@@ -232,12 +232,13 @@ def stoi(clean, est, fs_sig: int, extended: bool = False) -> float:
     return float(intelligibility(e, c, sample_rate=fs_sig)[0, 1 if extended else 0])
 
 
-class _ScorerType(type):
+class _ScorerType(_m._DecompressType):
     """``Scorer(..., intelligibility=True)``: the switch is a keyword of the class call, not of ``__init__``, whose parameter list
-    is pinned together with the other tools' (tests/test_resample_ref.py::test_defaults_of_the_tools_are_unchanged)."""
+    is pinned together with the other tools' (tests/test_resample_ref.py::test_defaults_of_the_tools_are_unchanged).
+    ``decompress`` is ``Enhancer``'s, named here so that the signature of the class shows it."""
 
-    def __call__(cls, *args, intelligibility: bool = False, distortion: bool = False, **kw):
-        self = super().__call__(*args, **kw)
+    def __call__(cls, *args, intelligibility: bool = False, distortion: bool = False, decompress: bool = False, **kw):
+        self = super().__call__(*args, decompress=decompress, **kw)
         self.intelligibility = bool(intelligibility)
         if distortion:                        # (off: the instance keeps the class's False and nothing else changes)
             self.distortion = True
@@ -266,7 +267,12 @@ class Scorer(Enhancer, metaclass=_ScorerType):
 
     ``distortion=True`` adds the keys ``sdr`` and ``sdr_mix`` after those: per batch, on the same stream, ``sdr`` (the SDR of
     BSS-eval with 512 taps) of the enhanced waves against the clean buffer with the lengths (hop * (T_b - 1), L_b), and of
-    noisy[ref_mic] against it with (L_b, L_b).  A file of fewer than 512 samples gives NaN in these two.  Off, nothing changes."""
+    noisy[ref_mic] against it with (L_b, L_b).  A file of fewer than 512 samples gives NaN in these two.  Off, nothing changes.
+
+    ``decompress=True`` (a bool; ``Enhancer``'s switch) takes the enhanced waves in the linear domain -- ``istft(decompress=True)``,
+    an estimate of the signal in the clean files -- and every wave score (``si_sdr, si_sir, si_sar, stoi, estoi, sdr``) on them.
+    ``loss`` stays the loss of the compressed spectra and keeps its bits; ``si_sdr_mix`` and ``sdr_mix`` do not see the
+    estimate.  The default False scores the reference's waves, whose spectra have square-rooted magnitudes."""
 
     intelligibility = False
     distortion = False

@@ -142,6 +142,26 @@ int eab_istft_lens_f32(const float* spec, const float* window, const float* twid
 int eab_istft_bwd_f32(const float* dwav, const float* window, const float* twiddle, float* dspec, const int32_t* lens,
                       int B, int T, int n_fft, int hop, eab_stream_t stream);
 
+/* The back end in the linear domain: eab_istft_f32 (lens == NULL) / eab_istft_lens_f32 (lens: DEVICE frame counts) applied to
+ *     y[b][:][t][f] = s * r,   s = (re, im) = spec[b][:][t][f],   r = sqrtf(re*re + im*im)   (products and sum rounded in fp32)
+ * which undoes the front end's X |X|^-1/2: the wave is an estimate of the signal itself, not of one with square-rooted
+ * magnitudes.  y is formed inside the kernel and never written to memory.  The modulus is the full one: the transform then
+ * ignores the imaginary parts of y at DC and Nyquist as before, so those parts of `spec` act through r only.
+ * Arguments, geometry limits and return codes as eab_istft_lens_f32; frames t >= lens[b] are never read, the samples after an
+ * utterance are zeros, and a row has the same bits alone and in any batch. */
+int eab_istft_lin_f32(const float* spec, const float* window, const float* twiddle, float* wav, const int32_t* lens,
+                      int B, int T, int n_fft, int hop, eab_stream_t stream);
+
+/* Its adjoint.  With g[b][:][t][k] what eab_istft_bwd_f32 writes for `dwav` (kept in registers) and s, r as above,
+ *     dspec[b][:][t][k] = r g + s (s . g) / r,   s . g = re g_re + im g_im;   exactly 0 where r == 0
+ * (y = s |s| is C1 with zero derivative at s = 0: no division, no NaN).  At k = 0 and k = n_fft/2, g_im = 0, so the imaginary
+ * gradient is im re g_re / r -- not forced to zero.
+ *   spec    [B][2][T][F]  the spectrum the forward was given; not read at frames t >= lens[b]
+ * Frames t >= lens[b] of dspec are zeros and dwav is never read behind a length; every element is stored once, no atomics.
+ * Limits and return codes as eab_istft_bwd_f32.  Entry points are added only: EAB_ABI_VERSION stays 10. */
+int eab_istft_lin_bwd_f32(const float* dwav, const float* spec, const float* window, const float* twiddle, float* dspec,
+                          const int32_t* lens, int B, int T, int n_fft, int hop, eab_stream_t stream);
+
 /* --------------------------------------------------------------------------
  * GaGNet post-filter glue (reference GaGNet.py).  The convolutions of the post-filter
  * run on eab_conv_f32; these are the two elementwise passes around them.
