@@ -207,6 +207,11 @@ _SIGS = {
     "eab_lstm64_bwd_lens_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "eab_filter_sum_ld_lens_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "eab_wgrad_batch_lens_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    # length-bucket training programs
+    "eab_gag_crm_bwd_lens_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
+    "eab_lstm64_train_fwd_lens_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_void_p]),
+    "eab_lstm64_train_fwd_lens_prec_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "eab_lstm64_bwd_bound_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_void_p]),
     "eab_cln_stats_f32": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_float] + [C.c_void_p] * 3 + [TimeWindow, C.c_void_p]),
     "eab_cln_apply_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [TimeWindow, C.c_void_p]),
     "eab_cln_step_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_float, TimeWindow, C.c_void_p]),

@@ -104,8 +104,11 @@ __global__ __launch_bounds__(GAG_THREADS) void gag_crm_bwd_kernel(const float* _
                                                                   const float* __restrict__ dplanar, const float* __restrict__ dpre_out,
                                                                   const float* __restrict__ acc_in, float* __restrict__ dg,
                                                                   float* __restrict__ dr, float* __restrict__ di,
-                                                                  float* __restrict__ dpre, int T, int F, int ld, int lin_ld, int act) {
+                                                                  float* __restrict__ dpre, int T, int F, int ld, int lin_ld, int act,
+                                                                  const int* __restrict__ lens) {
     const int b = blockIdx.x / T, t = blockIdx.x - b * T;
+    // padding frame of a per-utterance-length program: nothing of the frame is read, nothing written (its readers are masked)
+    if (lens && t >= lens[b]) return;
     const int bt = blockIdx.x;
     const size_t plane = (size_t)T * F;
     const float* d_r = dplanar ? dplanar + ((size_t)b * 2) * plane + (size_t)t * F : nullptr;
@@ -146,10 +149,17 @@ __global__ __launch_bounds__(GAG_THREADS) void gag_crm_bwd_kernel(const float* _
 extern "C" int eab_gag_crm_bwd_f32(const float* pre, const float* g, const float* dplanar, const float* dpre_out, const float* acc_in,
                                    float* dg, float* dr, float* di, float* dpre, int B, int T, int F, int ld, int lin_ld, int act,
                                    eab_stream_t stream) {
+    return eab_gag_crm_bwd_lens_f32(pre, g, dplanar, dpre_out, acc_in, dg, dr, di, dpre, B, T, F, ld, lin_ld, act, nullptr, stream);
+}
+
+// lens: device, B frame counts (NULL: every frame).  A workgroup whose frame lies behind lens[b] returns before its first load.
+extern "C" int eab_gag_crm_bwd_lens_f32(const float* pre, const float* g, const float* dplanar, const float* dpre_out,
+                                        const float* acc_in, float* dg, float* dr, float* di, float* dpre, int B, int T, int F, int ld,
+                                        int lin_ld, int act, const int32_t* lens, eab_stream_t stream) {
     EAB_CHECK_ARG(pre && g && dg && dr && di && (dplanar || dpre_out) && B > 0 && T > 0 && F > 0);
     EAB_CHECK_ARG(ld >= 2 * F && (ld % 4) == 0 && lin_ld >= F && (long long)B * T < (1ll << 31));
     EAB_CHECK_ARG(act == EAB_ACT_SIGMOID || act == EAB_ACT_TANH || act == EAB_ACT_RELU);
     hipLaunchKernelGGL(gag_crm_bwd_kernel, dim3(B * T), dim3(GAG_THREADS), 0, eab_stream(stream), pre, g, dplanar, dpre_out, acc_in, dg,
-                       dr, di, dpre, T, F, ld, lin_ld, act);
+                       dr, di, dpre, T, F, ld, lin_ld, act, lens);
     EAB_RETURN_LAUNCH_STATUS();
 }

@@ -495,7 +495,7 @@ extern "C" int eab_lstm64_stream_f32(const float* x, const float* ln_g, const fl
 // Training forward: the same layer (no LayerNorm inside: the training program materialises it, its output is an
 // operand of the weight gradient) that also stores the activated gates and cell states, gates [B*F][T][5][64].
 int eab_lstm64_bf_train_launch(const float* x, const float* wcat, const float* bias, float* h_out, float* gates, int T, int F, int S,
-                               hipStream_t stream);     // lstm_h3.hip
+                               const int* lens, hipStream_t stream);     // lstm_h3.hip
 
 extern "C" int eab_lstm64_train_fwd_f32(const float* x, const float* wcat, const float* bias, float* h_out, float* gates, int B,
                                         int T, int F, eab_stream_t stream) {
@@ -506,19 +506,32 @@ extern "C" int eab_lstm64_train_fwd_f32(const float* x, const float* wcat, const
 // accumulation, activations, cell state and stored gates (the arithmetic of torch.autocast(bfloat16) on nn.LSTM)
 extern "C" int eab_lstm64_train_fwd_prec_f32(const float* x, const float* wcat, const float* bias, float* h_out, float* gates, int B,
                                              int T, int F, int precision, eab_stream_t stream) {
+    return eab_lstm64_train_fwd_lens_prec_f32(x, wcat, bias, h_out, gates, nullptr, B, T, F, precision, stream);
+}
+
+// Per-utterance lengths (lens: device, B frame counts; NULL: the launch above): the recurrence of a workgroup stops after the
+// longest utterance among its sequences (eab_max_len, as in the inference kernels); rows of h_out and gates behind that step
+// are not written, and x there is not read.  Valid steps keep the bits of the launch without lengths.
+extern "C" int eab_lstm64_train_fwd_lens_f32(const float* x, const float* wcat, const float* bias, float* h_out, float* gates,
+                                             const int32_t* lens, int B, int T, int F, eab_stream_t stream) {
+    return eab_lstm64_train_fwd_lens_prec_f32(x, wcat, bias, h_out, gates, lens, B, T, F, EAB_PREC_F32, stream);
+}
+
+extern "C" int eab_lstm64_train_fwd_lens_prec_f32(const float* x, const float* wcat, const float* bias, float* h_out, float* gates,
+                                                  const int32_t* lens, int B, int T, int F, int precision, eab_stream_t stream) {
     EAB_CHECK_ARG(x && wcat && bias && h_out && gates && B > 0 && T > 0 && F > 0);
     EAB_CHECK_ARG(precision == EAB_PREC_F32 || precision == EAB_PREC_BF16);
     const long long S = (long long)B * F;
     EAB_CHECK_ARG(S * T * LS_H * 4 < (1ll << 31));
-    if (precision == EAB_PREC_BF16) return eab_lstm64_bf_train_launch(x, wcat, bias, h_out, gates, T, F, (int)S, eab_stream(stream));
+    if (precision == EAB_PREC_BF16) return eab_lstm64_bf_train_launch(x, wcat, bias, h_out, gates, T, F, (int)S, lens, eab_stream(stream));
     if (S <= 2048) {        // same split as the inference dispatcher: 4-sequence workgroups while they fit the chip in two rounds
         hipLaunchKernelGGL((lstm64_q_kernel<false, 1, true>), dim3((unsigned)((S + 3) / 4)), dim3(256), 0, eab_stream(stream), x,
-                           nullptr, nullptr, 0.0f, wcat, bias, h_out, T, F, (int)S, nullptr, 0, nullptr, gates);
+                           nullptr, nullptr, 0.0f, wcat, bias, h_out, T, F, (int)S, nullptr, 0, nullptr, gates, lens);
         EAB_RETURN_LAUNCH_STATUS();
     }
     const int grid = (int)((S + LS_SEQ - 1) / LS_SEQ);
     hipLaunchKernelGGL((lstm64_kernel<false, true>), dim3(grid), dim3(256), 0, eab_stream(stream), x, nullptr, nullptr, 0.0f, wcat,
-                       bias, h_out, T, F, (int)S, nullptr, 0, nullptr, gates);
+                       bias, h_out, T, F, (int)S, nullptr, 0, nullptr, gates, lens);
     EAB_RETURN_LAUNCH_STATUS();
 }
 

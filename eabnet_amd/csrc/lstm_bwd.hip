@@ -31,7 +31,10 @@ __device__ __forceinline__ float lb_tanh(float x) { return fmaf(2.0f, __builtin_
 // BF (the bf16 training programs): dgates_t and W_hh rounded to bf16, dh_rec on 8 v_mfma_f32_16x16x32_bf16 per wave instead of
 // 64 fp32 MFMAs of 32 cycles -- the recurrent product torch.autocast(bfloat16) runs for nn.LSTM's backward; the elementwise
 // chain, the carries and the dgates written for the weight / input gradients stay fp32.
-template <bool BF>
+// BOUND (the length-bucket training programs, whose width T is a cap): the walk starts at the last step of the longest utterance
+// among the workgroup's sequences instead of at T - 1 -- no recurrent product is spent on steps that only load zeros -- and the
+// dgates rows behind that step are LEFT ALONE (their readers are masked).  BOUND = false is the kernel as it was.
+template <bool BF, bool BOUND = false>
 __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict__ gates, const float* __restrict__ dh_out,
                                                          const float* __restrict__ wcat, float* __restrict__ dgates, int T, int F,
                                                          int S, const int* __restrict__ lens) {
@@ -41,6 +44,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
     const int ln = lane & 15, lk = lane >> 4;
     const int s0 = blockIdx.x * LB_SEQ;
     const int u = wave * 16 + ln;
+    const int t_top = (BOUND && lens) ? min(T, eab_max_len(lens, s0, LB_SEQ, S, F)) : T;
 
     // stationary operand: whT[4j+s] = W_hh[k = 16j + 4lk + s][u] = wcat[k][64 + u]
     // (BF: B fragments of the 16x16x32 form: whb[kb][j] = W_hh[k = 32kb + 8lk + j][u])
@@ -103,9 +107,9 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
         }
     };
 #pragma unroll
-    for (int k = 0; k < LB_PF; ++k) load(T - 1 - k, pf[k]);
+    for (int k = 0; k < LB_PF; ++k) load(t_top - 1 - k, pf[k]);
 
-    for (int t0 = T - 1; t0 >= 0; t0 -= LB_PF) {
+    for (int t0 = t_top - 1; t0 >= 0; t0 -= LB_PF) {
 #pragma unroll
       for (int k = 0; k < LB_PF; ++k) {
         const int t = t0 - k;
@@ -188,6 +192,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------------------------
 #define LBQ_LD (4 * LB_H + 4)
 
+template <bool BOUND = false>      // (see lstm64_bwd_kernel)
 __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restrict__ gates, const float* __restrict__ dh_out,
                                                            const float* __restrict__ wcat, float* __restrict__ dgates, int T, int F,
                                                            int S, const int* __restrict__ lens) {
@@ -199,6 +204,7 @@ __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restri
     const bool ok = sq < S;
     const int b = ok ? sq / F : 0, f = ok ? sq - b * F : 0;
     const int nt = lens ? min(lens[b], T) : T;                    // (per sequence: see lstm64_bwd_kernel)
+    const int t_top = (BOUND && lens) ? min(T, eab_max_len(lens, blockIdx.x * 4, 4, S, F)) : T;
     const size_t goff = ((size_t)(ok ? sq : 0) * T * 5) * LB_H + eu;
     const size_t hoff = (((size_t)b * T) * F + f) * LB_H + eu;
     const size_t g_t = (size_t)5 * LB_H, h_t = (size_t)F * LB_H;
@@ -234,9 +240,9 @@ __global__ __launch_bounds__(256) void lstm64_bwd_q_kernel(const float* __restri
         q[6] = ld(rs_h, v ? hb + (unsigned)t * h_tb : EAB_OOB);
     };
 #pragma unroll
-    for (int k = 0; k < LBQ_PF; ++k) load(T - 1 - k, pf[k]);
+    for (int k = 0; k < LBQ_PF; ++k) load(t_top - 1 - k, pf[k]);
 
-    for (int t0 = T - 1; t0 >= 0; t0 -= LBQ_PF) {
+    for (int t0 = t_top - 1; t0 >= 0; t0 -= LBQ_PF) {
 #pragma unroll
       for (int k = 0; k < LBQ_PF; ++k) {
         const int t = t0 - k;
@@ -313,26 +319,31 @@ extern "C" int eab_lstm64_bwd_prec_f32(const float* gates, const float* dh_out, 
 
 extern "C" int eab_lstm64_bwd_lens_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, const int32_t* lens,
                                        int B, int T, int F, int precision, eab_stream_t stream) {
+    return eab_lstm64_bwd_bound_f32(gates, dh_out, wcat, dgates, lens, 0, B, T, F, precision, stream);
+}
+
+// bound != 0 (needs lens): the recurrence of a workgroup starts at the longest length among its sequences; dgates rows behind it
+// are not written.  bound == 0 is eab_lstm64_bwd_lens_f32: every step walked, dgates of padding steps written as zeros.
+extern "C" int eab_lstm64_bwd_bound_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, const int32_t* lens,
+                                        int bound, int B, int T, int F, int precision, eab_stream_t stream) {
     EAB_CHECK_ARG(gates && dh_out && wcat && dgates && B > 0 && T > 0 && F > 0);
     EAB_CHECK_ARG(precision == EAB_PREC_F32 || precision == EAB_PREC_BF16);
     const long long S = (long long)B * F;
     EAB_CHECK_ARG(S * T * 5 * LB_H < (1ll << 40));
+    EAB_CHECK_ARG(bound == 0 || lens != nullptr);
     const int form = eab_lstm64_bwd_form(B, T, F, precision);
     // bf16: a step of the 16-sequence form is 8 short MFMAs instead of 64 long ones (742 vs 1004 us per layer at 2576 sequences);
     // up to 2048 sequences the 4-sequence fp32 kernel below is faster than either (655 vs 926 us at 966: four times the
     // workgroups, a quarter of the elementwise chain per lane) and exact, so small batches take it in every mode
+    const int grid = form == EAB_LSTM_BWD_FORM_Q ? (int)((S + 3) / 4) : (int)((S + LB_SEQ - 1) / LB_SEQ);
+#define LB_GO(...) hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)grid), dim3(256), 0, eab_stream(stream), gates, dh_out, wcat, dgates, T, F, (int)S, lens)
     if (form == EAB_LSTM_BWD_FORM_16_BF16) {
-        hipLaunchKernelGGL(lstm64_bwd_kernel<true>, dim3((unsigned)((S + LB_SEQ - 1) / LB_SEQ)), dim3(256), 0, eab_stream(stream), gates,
-                           dh_out, wcat, dgates, T, F, (int)S, lens);
-        EAB_RETURN_LAUNCH_STATUS();
+        if (bound) LB_GO(lstm64_bwd_kernel<true, true>); else LB_GO(lstm64_bwd_kernel<true, false>);
+    } else if (form == EAB_LSTM_BWD_FORM_Q) {
+        if (bound) LB_GO(lstm64_bwd_q_kernel<true>); else LB_GO(lstm64_bwd_q_kernel<false>);
+    } else {
+        if (bound) LB_GO(lstm64_bwd_kernel<false, true>); else LB_GO(lstm64_bwd_kernel<false, false>);
     }
-    if (form == EAB_LSTM_BWD_FORM_Q) {
-        hipLaunchKernelGGL(lstm64_bwd_q_kernel, dim3((unsigned)((S + 3) / 4)), dim3(256), 0, eab_stream(stream), gates, dh_out, wcat,
-                           dgates, T, F, (int)S, lens);
-        EAB_RETURN_LAUNCH_STATUS();
-    }
-    const int grid = (int)((S + LB_SEQ - 1) / LB_SEQ);
-    hipLaunchKernelGGL(lstm64_bwd_kernel<false>, dim3(grid), dim3(256), 0, eab_stream(stream), gates, dh_out, wcat, dgates, T, F, (int)S,
-                       lens);
+#undef LB_GO
     EAB_RETURN_LAUNCH_STATUS();
 }

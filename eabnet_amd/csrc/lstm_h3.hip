@@ -281,15 +281,15 @@ __global__ __launch_bounds__(256) void lstm64_h3_kernel(const float* __restrict_
 
 // training forward in bf16 (eab_lstm64_train_fwd_prec_f32, csrc/lstm.hip): the bf16 kernel that also stores the gates
 int eab_lstm64_bf_train_launch(const float* x, const float* wcat, const float* bias, float* h_out, float* gates, int T, int F, int S,
-                               hipStream_t stream) {
+                               const int* lens, hipStream_t stream) {
     // up to 4096 sequences (the training batch of configs[3] is 966): 4 sequences per workgroup -- the step is the cell update's
     // exp / rcp chain per lane, not the 16 MFMAs, and four times the workgroups quarter it (measured up to 2,576 sequences)
     if (S <= 4096)
         hipLaunchKernelGGL((lstm64_h3_kernel<false, true, true, 4>), dim3((S + 3) / 4), dim3(256), 0, stream, x, nullptr, nullptr, 0.0f,
-                           wcat, bias, h_out, T, F, S, nullptr, 0, nullptr, gates);
+                           wcat, bias, h_out, T, F, S, nullptr, 0, nullptr, gates, lens);
     else
         hipLaunchKernelGGL((lstm64_h3_kernel<false, true, true>), dim3((S + LH_SEQ - 1) / LH_SEQ), dim3(256), 0, stream, x, nullptr,
-                           nullptr, 0.0f, wcat, bias, h_out, T, F, S, nullptr, 0, nullptr, gates);
+                           nullptr, 0.0f, wcat, bias, h_out, T, F, S, nullptr, 0, nullptr, gates, lens);
     EAB_RETURN_LAUNCH_STATUS();
 }
 

@@ -307,6 +307,11 @@ class _HipModule(nn.Module):
         # lengths= under autograd: False = refused, as always; True = the training programs run with per-utterance
         # lengths (masked statistics, recurrences and weight gradients) -- EaBNet, is_causal=True, norm_type="IN"
         self.varlen_training = False
+        # length buckets for differentiable calls: None = nothing changes; "auto" (AUTO_BUCKETS) or an ascending
+        # tuple of caps.  A differentiable call of T frames, with or without lengths=, then runs on the masked training programs
+        # of the smallest cap >= T (wider calls: of width T) -- one lowering and one pair of graphs per (B, cap) for every
+        # narrower width and every combination of lengths.  EaBNet and GaGNet, is_causal=True, norm_type="IN"
+        self.train_length_buckets = None
 
     def _param_fingerprint(self) -> tuple:
         """Change detector for the packed weights (runs on every forward).  Every parameter / buffer slot
@@ -361,22 +366,40 @@ class _HipModule(nn.Module):
         return bound
 
     # -- per-utterance lengths / length buckets ----------------------------------------
-    def _bucket_caps(self) -> Tuple[int, ...]:
-        lb = self.length_buckets
+    def _bucket_caps(self, what: str = "length_buckets") -> Tuple[int, ...]:
+        lb = getattr(self, what)
         if lb is None:
             return ()
         if isinstance(lb, str):
             if lb != "auto":
-                raise ValueError(f"length_buckets must be None, 'auto' or an ascending tuple of frame counts, got {lb!r}")
+                raise ValueError(f"{what} must be None, 'auto' or an ascending tuple of frame counts, got {lb!r}")
             return AUTO_BUCKETS
-        caps = tuple(int(c) for c in lb)
+        try:
+            caps = tuple(int(c) for c in lb)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} must be None, 'auto' or an ascending tuple of frame counts, got {lb!r}") from None
         if not caps or any(c < 1 for c in caps) or any(b <= a for a, b in zip(caps, caps[1:])):
-            raise ValueError(f"length_buckets must be an ascending tuple of positive frame counts, got {lb!r}")
+            raise ValueError(f"{what} must be an ascending tuple of positive frame counts, got {lb!r}")
         return caps
+
+    def _train_bucket_call(self, T: int, B: int, lengths) -> Tuple[int, object]:
+        """(width of the program, lengths) of a differentiable call under train_length_buckets: the smallest cap >= T, or T
+        itself when it exceeds every cap; lengths=None means every utterance is T frames long.  Configurations the masked
+        training programs do not cover are refused here, before anything reaches a device."""
+        caps = self._bucket_caps("train_length_buckets")
+        lens = T if lengths is None else check_lengths(lengths, B, T)
+        from . import train
+        why = train.varlen_unsupported_reason(self.cfg)
+        if why:
+            raise NotImplementedError(f"{type(self).__name__}: a differentiable call with train_length_buckets: {why}")
+        cap = bucket_for(T, caps)
+        return (cap if cap is not None else T), lens
 
     def _varlen_call(self, T: int, B: int, lengths, needs_graph: bool) -> Optional[Tuple[int, object]]:
         """(T_cap, lengths) of a call that runs in a per-utterance-length program, or None for the exact-shape path.
         Explicit ``lengths`` are validated here (ValueError) and refused (NotImplementedError) where they cannot be served."""
+        if needs_graph and self.train_length_buckets is not None and not (self.varlen_training and self.length_buckets is not None):
+            return self._train_bucket_call(T, B, lengths)
         if lengths is None:
             if self.length_buckets is None or not self.cfg.is_causal or needs_graph or self.dump_bfw:
                 return None
@@ -444,6 +467,8 @@ class _HipModule(nn.Module):
             lower = self._training_lowering()
             self.training_backend = "hip"
             xs = tuple(x.detach().to(torch.float32).contiguous() for x in inputs)
+            if self.train_length_buckets is not None and vl is not None:
+                return train.forward_train(self, xs, lower, lengths=vl[1], cap=vl[0])
             return train.forward_train(self, xs, lower, lengths=None if (vl is None or lengths is None) else vl[1])
         if not all(x.is_cuda for x in inputs):
             raise _lib.EabError(f"eabnet_amd.{name} inference runs on MI355X only: move the {noun} (and module) to "
@@ -928,6 +953,16 @@ class EaBNetWithPostNet(nn.Module):
     def length_buckets(self, value) -> None:
         self.eabnet.length_buckets = value
         self.postnet.length_buckets = value
+
+    @property
+    def train_length_buckets(self):
+        """length buckets of both stages for differentiable calls (see EaBNet.train_length_buckets)"""
+        return self.eabnet.train_length_buckets
+
+    @train_length_buckets.setter
+    def train_length_buckets(self, value) -> None:
+        self.eabnet.train_length_buckets = value
+        self.postnet.train_length_buckets = value
 
     @property
     def varlen_training(self):

@@ -46,7 +46,7 @@ from .program import (NB_SUM_COPIES, NB_SUMS_ZEROED, OP_ADD, OP_CLN_BWD, OP_COLS
 from .spec import NetConfig, gate_key, param_specs
 
 MLP_LD = 64          # the second Linear of w_dnn is run with its 2M rows padded to one 64-column tile
-TRAIN_BOUND_CACHE = 3   # bound training programs kept per module (LRU over (B, T, F, device, precision, varlen))
+TRAIN_BOUND_CACHE = 3   # bound training programs kept per module (LRU over (B, T or cap, F, device, precision, varlen[, bucket]))
 
 
 def supported(cfg: NetConfig) -> bool:
@@ -955,25 +955,38 @@ class TrainProgram:
     # BatchNorm (train mode): (norm key, offset of the layer's batch (mean, rstd) table in the activation arena, C, samples)
     bn_layers: List[tuple] = field(default_factory=list)
     varlen: bool = False                     # the ops that sum or recurse across rows read per-utterance lengths (flag_varlen)
+    bucket: bool = False                     # T is a cap serving every call of T frames or fewer (train_length_buckets)
 
 
 # op kinds that honour eab_op.win.lens in the training programs, with the i[] slots that carry (B, T) where the op has none
 # (written by runtime.encode only together with the lengths pointer); the convolutions carry lens in their own descriptor
 VARLEN_KINDS = {OP_IN_STATS: ("T", 4), OP_NORM_BWD: ("T", 5), OP_LN_BWD: ("BT", 2), OP_LSTM_BWD: None, OP_FILTER_SUM: None,
-                OP_WGRAD: None}
+                OP_WGRAD: None, prg.OP_GAG_CRM_BWD: None}
+# (the post-filter's GAG_PACK and GAG_CRM are prg.GagPackOp / GagCrmOp: they have a `win` attribute of their own and honour lens)
+# the length-bucket form also bounds the two LSTM recurrences by the longest length of a workgroup: the forward
+# takes the pointer, the backward a flag in i[4] (written, like every lens_i slot, only together with the pointer)
+BUCKET_KINDS = {OP_LSTM_TRAIN: None, OP_LSTM_BWD: ("flag", 4)}
 
 
-def flag_varlen(prog: TrainProgram) -> TrainProgram:
+def flag_varlen(prog: TrainProgram, bucket: bool = False, lstm_bound: bool = True) -> TrainProgram:
     """Mark the readers that sum or recurse across rows: runtime.encode hands the lengths pointer of the binding
     to every op that has a ``win`` attribute.  The op lists themselves do not change; row-local ops stay unflagged (they carry
-    whatever the padding rows hold to padding rows only)."""
+    whatever the padding rows hold to padding rows only).  bucket: prog.T is a cap that serves every narrower call -- the LSTM
+    recurrences stop at the longest length of a workgroup (BUCKET_KINDS); lstm_bound=False leaves them walking the cap (what
+    tools/bench_train_buckets.py measures the bound against)."""
+    lstm = bucket and lstm_bound
     for op in list(prog.fwd) + list(prog.bwd):
         if op.kind in VARLEN_KINDS:
             op.win = False                                       # (no streaming window: the attribute is what encode looks for)
             slot = VARLEN_KINDS[op.kind]
             if slot is not None:
                 op.lens_i = {slot[1]: prog.T} if slot[0] == "T" else {slot[1]: prog.B, slot[1] + 1: prog.T}
+        if lstm and op.kind in BUCKET_KINDS:
+            op.win = False
+            if BUCKET_KINDS[op.kind] is not None:
+                op.lens_i = {BUCKET_KINDS[op.kind][1]: 1}
     prog.varlen = True
+    prog.bucket = bucket
     return prog
 
 
@@ -991,13 +1004,15 @@ def varlen_unsupported_reason(cfg) -> str:
     return ""
 
 
-def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "f32", varlen: bool = False) -> TrainProgram:
+def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "f32", varlen: bool = False,
+                bucket: bool = False, lstm_bound: bool = True) -> TrainProgram:
     """varlen: the same op list with the cross-row readers flagged for per-utterance lengths (flag_varlen); T is the padded
-    width.  Configurations outside is_causal=True / norm_type='IN' are refused."""
-    if varlen and varlen_unsupported_reason(cfg):
+    width.  bucket: the same with T a cap (the LSTM recurrences flagged too).  Configurations outside is_causal=True /
+    norm_type='IN' are refused."""
+    if (varlen or bucket) and varlen_unsupported_reason(cfg):
         raise NotImplementedError("training with per-utterance lengths: " + varlen_unsupported_reason(cfg))
     prog = TrainLowering(cfg, B, T, F, precision).build()
-    return flag_varlen(prog) if varlen else prog
+    return flag_varlen(prog, bucket, lstm_bound) if (varlen or bucket) else prog
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1080,18 +1095,38 @@ class TrainFn(torch.autograd.Function):
         ctx.serial = bound.serial
         x, x2 = inputs[0], (inputs[1] if len(inputs) > 1 else None)
         out_shape = prog.out_shape or (prog.B, 2, prog.T, prog.F)
-        if bound.use_graph and bound.capture(tuple(x.shape), out_shape, out_shape, None if x2 is None else tuple(x2.shape)):
-            bound.static["in"].copy_(x)
-            if x2 is not None:
-                bound.static["in2"].copy_(x2)
+        # a length-bucket program (prog.T is a cap) serves a call of Tc <= prog.T frames: the inputs go into the first Tc frames
+        # of its boundary buffers, the output's first Tc frames come back; what lies behind stays as it is (its readers are masked)
+        tax = 1 if x.ndim == 5 else 2
+        Tc = ctx.Tc = x.shape[tax]
+        wide = lambda t: None if t is None else tuple(t.shape[:tax]) + (prog.T,) + tuple(t.shape[tax + 1:])  # noqa: E731
+        if bound.use_graph and bound.capture(wide(x), out_shape, out_shape, wide(x2)):
+            if Tc == prog.T:
+                bound.static["in"].copy_(x)
+                if x2 is not None:
+                    bound.static["in2"].copy_(x2)
+            else:
+                bound.static["in"].narrow(tax, 0, Tc).copy_(x)
+                if x2 is not None:
+                    bound.static["in2"].narrow(tax, 0, Tc).copy_(x2)
             bound.graphs["fwd"].replay()
-            out = bound.static["out"].clone()
+            out = bound.static["out"].clone() if Tc == prog.T else bound.static["out"][..., :Tc, :].clone()
             ctx.io = None
         else:
+            if Tc != prog.T:
+                xw = x.new_empty(wide(x))
+                xw.narrow(tax, 0, Tc).copy_(x)
+                x = xw
+                if x2 is not None:
+                    x2w = x2.new_empty(wide(x2))
+                    x2w.narrow(tax, 0, Tc).copy_(x2)
+                    x2 = x2w
             out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
             ctx.io = (x, out, torch.empty_like(out), x2)
             bound.bind(*(None if t is None else t.data_ptr() for t in ctx.io))
             bound.run("fwd", st)
+            if Tc != prog.T:
+                out = out[..., :Tc, :].clone()
         ctx.bound = bound
         ctx.shapes = [p.shape for p in params]
         ctx.dtypes = [p.dtype for p in params]
@@ -1106,10 +1141,10 @@ class TrainFn(torch.autograd.Function):
                                "forward of the same module (one training program holds one set of activations)")
         bound.g.zero_()
         if ctx.io is None:
-            bound.static["dout"].copy_(grad_out)
+            (bound.static["dout"] if ctx.Tc == prog.T else bound.static["dout"][..., :ctx.Tc, :]).copy_(grad_out)
             bound.graphs["bwd"].replay()
         else:
-            ctx.io[2].copy_(grad_out.to(torch.float32))
+            (ctx.io[2] if ctx.Tc == prog.T else ctx.io[2][..., :ctx.Tc, :]).copy_(grad_out.to(torch.float32))
             bound.bind(*(None if t is None else t.data_ptr() for t in ctx.io))
             bound.run("bwd", st)
         gflat = torch.empty(prog.n_params, dtype=torch.float32, device=bound.device)     # fresh per call: .grad may keep views of it
@@ -1153,19 +1188,27 @@ def finish_flat_gradient(gflat: torch.Tensor, sync_group, shapes, dtypes, needs)
     return grads
 
 
-def forward_train(module, inputs: tuple, lower, lengths=None) -> torch.Tensor:
+def forward_train(module, inputs: tuple, lower, lengths=None, cap: Optional[int] = None) -> torch.Tensor:
     """A differentiable forward of ``module`` on its HIP training programs, lowered by ``lower(cfg, B, T, F, precision)``
     (lower_train here, train_gag.lower_train for GaGNet).  ``inputs``: fp32, contiguous, (B, T, F, M, 2) for EaBNet or two
     (B, 2, T, F) for GaGNet.  Returns the program's output arena ((B, 2, T, F), or (q, B, 2, T, F) for GaGNet).
     ``lengths`` (checked by model.check_lengths: a list or a device tensor of B frame counts): the program lowered with
-    varlen=True, its lengths array written on the current stream before the forward replay -- no host synchronisation."""
+    varlen=True, its lengths array written on the current stream before the forward replay -- no host synchronisation.
+    ``cap`` (train_length_buckets, DESIGN §4.27): the program lowered with bucket=True at width ``cap`` >= T serves the call;
+    ``lengths`` is then a list, a device tensor or one int for every utterance; returned tensors have the call's width T."""
     _lib.load()
     x = inputs[0]
     B, T, F = (x.shape[0], x.shape[1], x.shape[2]) if x.ndim == 5 else (x.shape[0], x.shape[2], x.shape[3])
     cache = module.__dict__.setdefault("_train_bound", {})
     prec = "bf16" if module.precision == "bf16" else "f32"
     varlen = lengths is not None
-    key = (B, T, F, str(x.device), prec, varlen)
+    bucket = cap is not None
+    assert not bucket or (varlen and cap >= T)
+    Tp = cap if bucket else T                          # the width of the program
+    # (a bucket program's key carries the cap in place of T and one more member, the bucket flag; the others keep their form)
+    # (module.train_bucket_lstm_bound = False, a measurement switch: the bucket program with both LSTM recurrences walking the cap)
+    lstm_bound = bool(getattr(module, "train_bucket_lstm_bound", True))
+    key = (B, Tp, F, str(x.device), prec, varlen) + (((True,) if lstm_bound else ("lstm_walks_cap", True)) if bucket else ())
     bound = cache.pop(key, None)
     if bound is None:
         # a small LRU of bound programs (variable-length batches, a smaller last batch, alternating train / validation
@@ -1174,7 +1217,9 @@ def forward_train(module, inputs: tuple, lower, lengths=None) -> torch.Tensor:
             torch.cuda.synchronize(x.device)      # the dropped program's arenas may still be read by kernels in flight
             cache.pop(next(iter(cache)))
         with torch.cuda.device(x.device):
-            bound = TrainBound(lower(module.cfg, B, T, F, prec, varlen=True) if varlen else lower(module.cfg, B, T, F, prec), x.device)
+            prog = (lower(module.cfg, B, Tp, F, prec, bucket=True, lstm_bound=lstm_bound) if bucket else
+                    lower(module.cfg, B, T, F, prec, varlen=True) if varlen else lower(module.cfg, B, T, F, prec))
+            bound = TrainBound(prog, x.device)
     cache[key] = bound                               # most recently used last
     bound.use_graph = bool(getattr(module, "use_graph", True)) and not torch.cuda.is_current_stream_capturing()
     sd = dict(module.named_parameters())
@@ -1182,7 +1227,9 @@ def forward_train(module, inputs: tuple, lower, lengths=None) -> torch.Tensor:
     sync = module.__dict__.get("grad_allreduce", None)          # None | True (default group) | a process group
     with torch.cuda.device(x.device):
         if varlen:
-            if isinstance(lengths, torch.Tensor):
+            if isinstance(lengths, int):
+                bound.lens.fill_(lengths)
+            elif isinstance(lengths, torch.Tensor):
                 bound.lens.copy_(lengths.to(torch.int32), non_blocking=True)
             else:
                 bound.lens.copy_(torch.as_tensor(lengths, dtype=torch.int32).pin_memory(), non_blocking=True)

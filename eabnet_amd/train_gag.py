@@ -190,5 +190,13 @@ class GagTrainLowering(TrainLowering):
         return prog
 
 
-def lower_train(cfg: GagConfig, B: int, T: int, F: int = 161, precision: str = "f32") -> TrainProgram:
-    return GagTrainLowering(cfg, B, T, F, precision).build()
+def lower_train(cfg: GagConfig, B: int, T: int, F: int = 161, precision: str = "f32", varlen: bool = False,
+                bucket: bool = False, lstm_bound: bool = True) -> TrainProgram:
+    """varlen / bucket: the same op list with every op that sums across rows flagged for per-utterance lengths (train.flag_varlen,
+    DESIGN §4.27: the convolutions, in1d, the norm backward, the weight gradients, and the pack / CRM / CRM backward of this
+    file, which skip padding frames); T is the padded width, with bucket a cap.  The three parallel lanes read one lengths
+    array.  Configurations outside is_causal=True / norm_type='IN' are refused with train.varlen_unsupported_reason."""
+    if (varlen or bucket) and tr.varlen_unsupported_reason(cfg):
+        raise NotImplementedError("training with per-utterance lengths: " + tr.varlen_unsupported_reason(cfg))
+    prog = GagTrainLowering(cfg, B, T, F, precision).build()
+    return tr.flag_varlen(prog, bucket, lstm_bound) if (varlen or bucket) else prog      # (lstm_bound: the post-filter has no LSTM)

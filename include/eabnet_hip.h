@@ -190,6 +190,11 @@ int eab_gag_crm_f32(const float* pre, const float* g, const float* r, const floa
 int eab_gag_crm_bwd_f32(const float* pre, const float* g, const float* dplanar, const float* dpre_out, const float* acc_in,
                         float* dg, float* dr, float* di, float* dpre, int B, int T, int F, int ld, int lin_ld, int act,
                         eab_stream_t stream);
+/* the same under per-utterance lengths (lens: DEVICE, B frame counts, NULL = the call above, bit for bit): a frame t >= lens[b]
+ * is neither read (dplanar, dpre_out, pre, g, acc_in) nor written (dg, dr, di, dpre). */
+int eab_gag_crm_bwd_lens_f32(const float* pre, const float* g, const float* dplanar, const float* dpre_out, const float* acc_in,
+                             float* dg, float* dr, float* di, float* dpre, int B, int T, int F, int ld, int lin_ld, int act,
+                             const int32_t* lens, eab_stream_t stream);
 
 /* --------------------------------------------------------------------------
  * Training loss, value and gradient in one pass (first piece).  Replaces com_mag_mse_loss
@@ -985,6 +990,18 @@ int eab_lstm64_bwd_lens_f32(const float* gates, const float* dh_out, const float
 int eab_filter_sum_ld_lens_f32(const float* w, const float* x, float* y, int B, int T, int F, int M, int ld, const int32_t* lens,
                                eab_stream_t stream);
 int eab_wgrad_batch_lens_f32(const eab_wgrad_desc* descs, int n, int stride_bytes, const int32_t* lens, eab_stream_t stream);
+/* Length-bucket training programs (the program width T is a cap): the two LSTM recurrences bounded by the longest
+ * utterance among a workgroup's sequences (sequence s belongs to utterance s / F).
+ *   lstm64_train_fwd_lens: steps behind that length are not run -- x there is not read, h_out and gates there not written;
+ *     the steps that run keep the bits of the launch without lengths.  lens == NULL is eab_lstm64_train_fwd_prec_f32.
+ *   lstm64_bwd_bound: bound == 0 is eab_lstm64_bwd_lens_f32; bound != 0 (needs lens) starts the reverse walk at that length and
+ *     leaves the dgates rows behind it alone (steps between a shorter sequence's own length and it are still written as zeros). */
+int eab_lstm64_train_fwd_lens_f32(const float* x, const float* wcat, const float* bias, float* h_out, float* gates,
+                                  const int32_t* lens, int B, int T, int F, eab_stream_t stream);
+int eab_lstm64_train_fwd_lens_prec_f32(const float* x, const float* wcat, const float* bias, float* h_out, float* gates,
+                                       const int32_t* lens, int B, int T, int F, int precision, eab_stream_t stream);
+int eab_lstm64_bwd_bound_f32(const float* gates, const float* dh_out, const float* wcat, float* dgates, const int32_t* lens,
+                             int bound, int B, int T, int F, int precision, eab_stream_t stream);
 
 /* Weight gradient on fp32 MFMA:
  *   dw[n][tap*UPT*16 + c] += sum_{b,t,o} dz[b][t][o*ostride+ophase][n] * src[b][t+dt_tap][o*istride+ioff_tap][c]
