@@ -37,9 +37,14 @@
 #define CG_DUAL 2    // value/gate columns see the SAME source through two transforms (S-TCM branches)
 #define CG_PH2 3     // EAB_EPI_PHASE2: the two output-column phases of a stride-2 transposed convolution from ONE staged input
                      // patch: column pairs (phase 0, phase 1) of a channel share a lane like (value, gate) of the GLU form
+#define CG_PH2S 4    // CG_PH2 for a patch of at most CG_PSHORT positions: four patch passes instead of six -- eight registers of
+                     // staged patch and two entries of every per-pass array less --, and a patch area of that size
 #define CG_XFC 128   // max channels of a source that carries a fused transform
 
 #define CG_PMAX 352  // input positions of one patch (PATCH mode): 352 * 80 B = 27.5 KB, three workgroups per CU
+#define CG_PSHORT 256 // input positions of one patch of the short phase-pair form (CG_PH2S)
+
+constexpr bool cg_ph2(int mode) { return mode == CG_PH2 || mode == CG_PH2S; }
 
 template <int MI, int NI, int KU, int MODE, bool PATCH, bool XFT>
 struct CgSmem {
@@ -47,8 +52,9 @@ struct CgSmem {
     static constexpr int NA = MODE == CG_DUAL ? 2 : 1;
     static constexpr int ATILE = BM * LDK;                       // one A tile (floats)
     // gather mode: NA x 2 (double-buffered) A tiles of BM output rows;
-    // patch mode: ONE tile of CG_PMAX input positions, re-read by every tap of a channel chunk
-    float a[PATCH ? CG_PMAX * LDK : NA * 2 * ATILE];
+    // patch mode: ONE tile of PMAX input positions, re-read by every tap of a channel chunk
+    static constexpr int PMAX = MODE == CG_PH2S ? CG_PSHORT : CG_PMAX;
+    float a[PATCH ? PMAX * LDK : NA * 2 * ATILE];
     float b[2][BN * LDK];
     float xft[2][CG_XFC][2];     // (scale, shift) per channel: table 0 = src0 / left, 1 = src1 / right
     float xsl[2][CG_XFC];        // PReLU slopes
@@ -58,7 +64,7 @@ struct CgSmem {
     // the epilogue's row table (one word per tile row, two in the phase-pair form): a launch without a fused transform
     // (XFT false) keeps it in the unused transform tables, so the gated 128x128 tiles' LDS -- three workgroups per CU --
     // stays what it was
-    static constexpr int RW = MODE == CG_PH2 ? 2 : 1;
+    static constexpr int RW = cg_ph2(MODE) ? 2 : 1;
     __attribute__((aligned(16))) unsigned rtab_own[XFT ? BM * RW : 4];
     static_assert(XFT || sizeof(float) * 2 * CG_XFC * 2 >= sizeof(unsigned) * BM * RW, "row table inside xft");
 };
@@ -80,14 +86,15 @@ __device__ __forceinline__ void cg_merge(float& n, float& mean, float& m2, float
 // 32-channel units -- a compile-time property of the launch, so that the loads of a stage stay one straight-line burst (a
 // run-time flag around them measured slower: the weight-gradient kernel lost 30 % to exactly that)
 template <int MI, int NI, int KU, int MODE, int XF, bool VEC, int PREC, bool PATCH, bool WIDE = false>
-__global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE == CG_GLU) ? 3 : (MODE == CG_PH2 ? 2 : 1)) void conv_gemm_kernel(const eab_conv_desc d) {
+__global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE == CG_GLU) ? 3 : (cg_ph2(MODE) ? 2 : 1)) void conv_gemm_kernel(const eab_conv_desc d) {
     // (workgroups per CU the register budget is cut for: three for the gated 128x128 tiles -- 168 registers, no spills --, two
-    // for the phase-pair form, whose fused transform and second store stream do not fit 168)
-    static_assert(MODE != CG_PH2 || (PATCH && NI == 2), "phase-pair form: patch pipeline, one column block per phase and wave");
+    // for the phase-pair form: a floor for its f16x3 / bf16 instances.  The exact-fp32 ones are not forced below it, they
+    // build to 142 (CG_PH2S) / 152 registers by their structure (pcompute_ph2) and run three per CU; the Makefile checks it)
+    static_assert(!cg_ph2(MODE) || (PATCH && NI == 2), "phase-pair form: patch pipeline, one column block per phase and wave");
     static_assert(!PATCH || (KU == 1 && MODE != CG_DUAL && VEC), "patch mode: one unit per stage, single transform");
     constexpr bool H3 = PREC == EAB_PREC_F16X3;
     constexpr bool BF = PREC == EAB_PREC_BF16;       // fp32 in memory, operands rounded to bf16 on their way into LDS, ONE bf16 MFMA
-    constexpr bool PH2 = MODE == CG_PH2;            // (phase 0, phase 1) column pair per lane; own epilogue
+    constexpr bool PH2 = cg_ph2(MODE);              // (phase 0, phase 1) column pair per lane; own epilogue
     constexpr bool GLU = MODE != CG_PLAIN;          // paired columns per lane: gated epilogue (value tile, gate tile) / phase pair
     constexpr bool DUAL = MODE == CG_DUAL;
     using Smem = CgSmem<MI, NI, KU, MODE, PATCH, XF != EAB_XF_NONE>;
@@ -158,46 +165,11 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             rtab[tid] = off;
     }
 
-    if (XF != EAB_XF_NONE) {
-        // (scale, shift, slope) tables of this batch element -> LDS.  Either the host ran
-        // eab_in_finalize_f32 (xf0/xf1) or the producer left few enough tiles that every
-        // consumer workgroup reduces them itself (fin_stats; fp64, fixed order, so all
-        // workgroups and the stand-alone kernel agree bit for bit).
-        const int k = tid >> 7, c = tid & (CG_XFC - 1);
-        const int Ck = (k == 0 || DUAL) ? d.C0 : d.C1;
-        const float* xfk = k == 0 ? d.xf0 : d.xf1;
-        const float* slk = k == 0 ? d.slope0 : d.slope1;
-        float sc = 1.0f, sh = 0.0f, sl = 1.0f;
-        if (c < Ck) {
-            if (d.fin_stats && k < d.fin_nsets) {
-                const float* gm = k == 0 ? d.fin_gamma0 : d.fin_gamma1;
-                const float* bt = k == 0 ? d.fin_beta0 : d.fin_beta1;
-                double sn = 0.0, sm = 0.0, sq = 0.0;            // same exact merge as in_finalize_kernel
-                for (int t = 0; t < d.fin_tiles; ++t) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(
-                        &d.fin_stats[((((size_t)b * d.fin_tiles + t) * d.fin_nsets + k) * d.C0 + c) * 4]);
-                    const double n = (double)v[0], mu = (double)v[1];
-                    sn += n;
-                    sm = fma(n, mu, sm);
-                    sq += fma(n * mu, mu, (double)v[2]);
-                }
-                const double mean = sn > 0.0 ? sm / sn : 0.0;
-                double var = sn > 0.0 ? sq / sn - mean * mean : 0.0;
-                if (var < 0.0) var = 0.0;
-                const double scale = (double)gm[c] / sqrt(var + (double)d.fin_eps);
-                sc = (float)scale;
-                sh = (float)((double)bt[c] - mean * scale);
-                sl = slk[c];
-            } else if (xfk) {
-                const float2 v = *reinterpret_cast<const float2*>(&xfk[((size_t)b * Ck + c) * 2]);
-                sc = v.x;
-                sh = v.y;
-                sl = slk[c];
-            }
-        }
-        sm.xft[k][c][0] = sc;
-        sm.xft[k][c][1] = sh;
-        sm.xsl[k][c] = sl;
+    // The transform tables are filled here, or -- EARLY: a tile of the PATCH or the LEAN gather pipeline -- behind the tile's
+    // first loads (conv_gemm_xf.inc, included as text: one statement of the code, the same instructions at either place).
+    constexpr bool EARLY = PATCH || (KU == 1 && VEC && !DUAL);   // the PATCH and the LEAN gather pipeline
+    if constexpr (!EARLY) {
+#include "conv_gemm_xf.inc"
     }
 
     const int Ctot = d.C0 + d.C1;
@@ -244,7 +216,11 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     // (__syncthreads() would add s_waitcnt vmcnt(0) and drain the prefetch).
     auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
-    __syncthreads();   // tap tables (and transform tables) visible
+    // tap tables (and transform tables) visible.  A tile of the PATCH or the LEAN gather pipeline has its first loads in flight
+    // before it fills the transform tables and meets this barrier inside its pipeline, without draining them; one with no row
+    // to compute meets it here.
+    if constexpr (!EARLY) __syncthreads();
+    else if (q0 >= Q) lds_barrier();
 
     // A tile wholly past the rows to compute (streaming window past the utterance end, padding frames of a per-utterance
     // length) skips the main loop: its accumulators stay zero, the epilogue stores nothing and the partial counts n = 0.
@@ -259,7 +235,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         // weights stream per stage.  Versus the gather pipeline this removes the ntaps-fold
         // re-fetch / re-transform / re-split of A.
         // ------------------------------------------------------------------------------
-        constexpr int PP = (CG_PMAX + 63) / 64;
+        constexpr int PP = (Smem::PMAX + 63) / 64;
         int dt_min = 0, io_min = 0, io_max = 0;
 #pragma unroll
         for (int j = 0; j < EAB_MAX_TAPS; ++j)
@@ -274,7 +250,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
         const float inv_fp = 1.0f / (float)Fp;
         const int t_first = eab_div(q0, d.No, inv_no);
         const int t_last = eab_div((q0 + BM < Q ? q0 + BM : (Q > q0 ? Q : q0 + 1)) - 1, d.No, inv_no);
-        const int P = (t_last - t_first + 1 - dt_min) * Fp;          // <= CG_PMAX (checked on the host)
+        const int P = (t_last - t_first + 1 - dt_min) * Fp;          // <= Smem::PMAX (checked on the host)
 
         // Patch row pidx = srow + 64*pp of pass pp is (t_in, f) = divmod(pidx, Fp): one division per thread, then a step of 64
         // positions per pass -- 64 = d64*Fp + m64 (workgroup-uniform), one wrap test.  A pass with 64*pp >= P (workgroup-uniform)
@@ -346,7 +322,7 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
 #pragma unroll
             for (int pp = 0; pp < PP; ++pp) {
                 const int pidx = srow + 64 * pp;
-                if (pidx >= CG_PMAX) continue;
+                if (pidx >= Smem::PMAX) continue;
                 if (64 * pp >= P) continue;                          // dead pass (workgroup-uniform)
                 f32x4 v = rp[pp];
                 if (XF != EAB_XF_NONE) {
@@ -449,13 +425,49 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
             }
         };
         const unsigned p2mask = PH2 ? (unsigned)d.p2_mask1 : ~0u;
+        // Exact-fp32 phase pair, one column block at a time: the phase-0 block of every tap, then the phase-1 block behind a
+        // (wave-uniform) branch on the tap's mask bit.  Two whole variants of the stage, (block 0) and (blocks 0, 1), met at a
+        // merge of all 64 accumulators, which the compiler answered with a second accumulator set -- 128 registers, two
+        // workgroups per CU; this way the accumulators are updated in place.  Every accumulator still takes its k-steps in the
+        // order g, k -- the blocks are independent sums, so no bit of the result moves.
+        auto pcompute_ph2 = [&](int cur, int tap) {
+            const int toff = (sm.dt[tap] * Fp + sm.ioff[tap]) * LDK;
+            f32x4 af[2][MI];
+#pragma unroll
+            for (int g = 0; g < 2; ++g)
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) af[g][mi] = *reinterpret_cast<const f32x4*>(&sm.a[fa[mi] + toff + g * 8]);
+            auto block = [&](auto ni_c) {
+                constexpr int ni = decltype(ni_c)::value;
+#pragma unroll
+                for (int g = 0; g < 2; ++g) {
+                    const f32x4 bf = *reinterpret_cast<const f32x4*>(&sm.b[cur][b_base + ni * 32 * LDK + g * 8]);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k)
+#pragma unroll
+                        for (int mi = 0; mi < MI; ++mi)
+                            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[g][mi][k], bf[k], acc[mi][ni], 0, 0, 0);
+                }
+            };
+            block(std::integral_constant<int, 0>{});
+            if ((p2mask >> tap) & 1u) block(std::integral_constant<int, NI - 1>{});
+        };
         auto pcompute = [&](int cur, int tap) {
-            if (PH2 && !((p2mask >> tap) & 1u)) pcompute_n(cur, tap, std::integral_constant<int, 1>{});   // (wave-uniform)
+            if constexpr (PH2 && !BF && !H3) pcompute_ph2(cur, tap);
+            else if (PH2 && !((p2mask >> tap) & 1u)) pcompute_n(cur, tap, std::integral_constant<int, 1>{});   // (wave-uniform)
             else pcompute_n(cur, tap, std::integral_constant<int, NI>{});
         };
 
+        // One memory round trip before the first MFMA, not two: neither the patch addresses nor the weight addresses depend
+        // on a table in LDS (the taps are read from the descriptor, p_tf / p_ok are integer arithmetic), so the first patch and
+        // the first weights are requested BEFORE the transform tables are fetched and the kernel's first barrier is met; that
+        // barrier waits for LDS only.  patch_stash reads the tables behind it.
         patch_fetch(0);
         b_fetch(0, rbw0);
+        {
+#include "conv_gemm_xf.inc"
+        }
+        lds_barrier();
         patch_stash();
         b_stash(0, rbw0);
         b_fetch(1, rbw0);                                            // stage u+1 -> rbw0, stage u+2 -> rbw1
@@ -528,29 +540,31 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     unsigned w_off[NI];
 #pragma unroll
     for (int p = 0; p < NI; ++p) w_off[p] = (unsigned)((n_blk + srow + 64 * p) * d.Kpad + skq * 4) * 4u;
+    auto tap_enter = [&](int dt, int io) {                      // LEAN: the row state of a tap
+#pragma unroll
+        for (int p = 0; p < MI; ++p) {
+            const int tt = a_t[p] + dt, fi = a_f0[p] + io;
+            tap_ok[p] = a_ok[p] && tt >= 0 && tt < t_src && fi >= 0 && fi < d.Fin;
+            const unsigned pos = (unsigned)(a_tf[p] + dt * d.Fin + io);
+            tap_b0[p] = (pos * (unsigned)d.C0 + (unsigned)(skq * (w0 ? 8 : 4))) * esz0;
+            tap_b1[p] = (pos * (unsigned)d.C1 + (unsigned)(skq * (w1 ? 8 : 4))) * esz1;
+        }
+    };
     auto fetch = [&](int stage, Stage& rg) {
         if constexpr (LEAN) {
             // (callers never ask for a stage past the last one; g_w = channels of the previous unit: 16, or 32 for a bf16 source)
             if (stage == 0) {
+                // the first gather is issued BEFORE the kernel's first barrier (below): tap 0 from the descriptor, not from LDS
                 g_tap = 0;
                 g_c0 = 0;
+                tap_enter(d.dt[0], d.ioff[0]);
             } else {
                 g_c0 += g_w;
                 if (g_c0 >= (UPT << 4)) {
                     g_c0 = 0;
                     ++g_tap;
                 }
-            }
-            if (g_c0 == 0) {                                    // (workgroup-uniform) first unit of a tap
-                const int dt = sm.dt[g_tap], io = sm.ioff[g_tap];
-#pragma unroll
-                for (int p = 0; p < MI; ++p) {
-                    const int tt = a_t[p] + dt, fi = a_f0[p] + io;
-                    tap_ok[p] = a_ok[p] && tt >= 0 && tt < t_src && fi >= 0 && fi < d.Fin;
-                    const unsigned pos = (unsigned)(a_tf[p] + dt * d.Fin + io);
-                    tap_b0[p] = (pos * (unsigned)d.C0 + (unsigned)(skq * (w0 ? 8 : 4))) * esz0;
-                    tap_b1[p] = (pos * (unsigned)d.C1 + (unsigned)(skq * (w1 ? 8 : 4))) * esz1;
-                }
+                if (g_c0 == 0) tap_enter(sm.dt[g_tap], sm.ioff[g_tap]);   // (workgroup-uniform) first unit of a tap
             }
             const bool second = (d.C1 > 0) && (g_c0 >= d.C0);  // workgroup-uniform
             const int Cs = second ? d.C1 : d.C0;
@@ -730,6 +744,10 @@ __global__ __launch_bounds__(CG_THREADS, (MI == 2 && NI == 2 && KU == 1 && MODE 
     };
 
     fetch(0, sa);
+    if constexpr (EARLY) {          // (as in the PATCH pipeline: one memory round trip before the first MFMA, not two)
+#include "conv_gemm_xf.inc"
+        lds_barrier();
+    }
     stash(0, sa);
     lds_barrier();
 
@@ -1235,7 +1253,10 @@ static int cg_launch(const eab_conv_desc* d, hipStream_t s) {
     dim3 grid((unsigned)(d->B * tiles), (unsigned)(d->N / BN));
     constexpr bool can_patch = KU == 1 && MODE != CG_DUAL && VEC && XF != EAB_XF_PRELU_NORM;
     if (d->korder == EAB_KORDER_CHUNK) {
-        if constexpr (can_patch) {
+        if constexpr (MODE == CG_PH2S) {          // the short phase-pair form exists on exact fp32 only (eab_conv_f32 picks it)
+            hipLaunchKernelGGL((conv_gemm_kernel<MI, NI, 1, MODE, XF, true, EAB_PREC_F32, true>), grid, dim3(CG_THREADS), 0, s, *d);
+            EAB_RETURN_LAUNCH_STATUS();
+        } else if constexpr (can_patch) {
             if (d->precision == EAB_PREC_F16X3)
                 hipLaunchKernelGGL((conv_gemm_kernel<MI, NI, 1, MODE, XF, true, EAB_PREC_F16X3, true>), grid,
                                    dim3(CG_THREADS), 0, s, *d);
@@ -1250,8 +1271,8 @@ static int cg_launch(const eab_conv_desc* d, hipStream_t s) {
             return EAB_EUNSUPPORTED;
         }
     }
-    if constexpr (MODE == CG_PH2) {
-        return EAB_EUNSUPPORTED;                 // the phase-pair form exists in the patch pipeline only
+    if constexpr (cg_ph2(MODE)) {
+        return EAB_EUNSUPPORTED;                // the phase-pair form exists in the patch pipeline only
     } else {
     if (d->precision == EAB_PREC_F16X3) {
         if constexpr (VEC)
@@ -1410,6 +1431,13 @@ extern "C" int eab_conv_f32(const eab_conv_desc* d, eab_stream_t stream) {
     if (ku == 2 && (!vec || dual)) ku = 1;
     if (ph2) {
         if (!vec || xf == EAB_XF_PRELU_NORM) return EAB_EUNSUPPORTED;
+        // a patch of at most CG_PSHORT positions (every phase-pair launch of the 161-bin network) on exact fp32: the four-pass
+        // instance (10 registers and 7.5 KB of LDS less); anything larger keeps the six-pass one (phase_pair_passes, program.py)
+        if (d->precision == EAB_PREC_F32 && cg_patch_positions(d) <= CG_PSHORT) {
+            if (xf == EAB_XF_NORM_PRELU)
+                return mi == 2 ? cg_launch<2, 2, 1, CG_PH2S, EAB_XF_NORM_PRELU, true>(d, s) : cg_launch<1, 2, 1, CG_PH2S, EAB_XF_NORM_PRELU, true>(d, s);
+            return mi == 2 ? cg_launch<2, 2, 1, CG_PH2S, EAB_XF_NONE, true>(d, s) : cg_launch<1, 2, 1, CG_PH2S, EAB_XF_NONE, true>(d, s);
+        }
         if (xf == EAB_XF_NORM_PRELU)
             return mi == 2 ? cg_launch<2, 2, 1, CG_PH2, EAB_XF_NORM_PRELU, true>(d, s) : cg_launch<1, 2, 1, CG_PH2, EAB_XF_NORM_PRELU, true>(d, s);
         return mi == 2 ? cg_launch<2, 2, 1, CG_PH2, EAB_XF_NONE, true>(d, s) : cg_launch<1, 2, 1, CG_PH2, EAB_XF_NONE, true>(d, s);

@@ -55,6 +55,7 @@ KORDER_TAP, KORDER_CHUNK, KORDER_FRAG = 0, 1, 2
 # 768-deep first phase of the last decoder measured slower there than on 128-row tiles (C1: 2.89 vs 2.75 ms per utterance)
 ST_GLU_KMAX = 512
 PATCH_MAX = 352    # CG_PMAX in csrc/conv_gemm.hip
+PATCH_SHORT = 256  # CG_PSHORT: the phase-pair launches up to here run the four-pass instance (phase_pair_passes)
 EPS_IN = 1e-5      # nn.InstanceNorm*d default (reference EaBNet.py:684,686)
 EPS_LN = 1e-5      # nn.LayerNorm default (reference EaBNet.py:598)
 ALIGN = 64         # floats: every arena allocation starts on a 256-byte boundary
@@ -506,6 +507,16 @@ def patch_positions(bm: int, No: int, Fin: int, istride: int, dt, ioff) -> int:
     hi_need = (No - 1) * istride + io_max - (Fin - 1)
     Fp = Fin - io_min + max(hi_need, 0)
     return ((bm - 1) // No + 2 - dt_min) * Fp
+
+
+def phase_pair_passes(op: "ConvOp") -> int:
+    """patch passes (of 64 positions) of the phase-pair instance that eab_conv_f32 picks for an EPI_PHASE2 launch: the short
+    instance -- four passes, a patch of at most PATCH_SHORT positions, exact fp32 -- or the six-pass one for anything larger
+    and for the f16x3 / bf16 products.  The launch carries no word for it: the entry point decides from the same positions."""
+    assert op.epi == EPI_PHASE2 and op.korder == KORDER_CHUNK
+    P = patch_positions(op.bm, op.No, op.Fin, op.istride, op.dt, op.ioff)
+    assert P <= PATCH_MAX
+    return 4 if op.precision == PREC_F32 and P <= PATCH_SHORT else 6
 
 
 # ----------------------------------------------------------------------------
