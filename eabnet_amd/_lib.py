@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libeabnet_hip.so")
 ABI_VERSION = 10
 MAX_TAPS = 16
+EAB_EUNSUPPORTED = 2     # status code: valid arguments the library has no kernel for (include/eabnet_hip.h)
 _fp = C.POINTER(C.c_float)
 
 
@@ -206,6 +207,8 @@ _SIGS = {
     "eab_layernorm64_bwd_lens_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "eab_lstm64_bwd_lens_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "eab_filter_sum_ld_lens_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "eab_input_grad_f32": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "eab_stft_compress_bwd_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.c_void_p]),
     "eab_wgrad_batch_lens_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     # length-bucket training programs
     "eab_gag_crm_bwd_lens_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),

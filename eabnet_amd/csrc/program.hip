@@ -203,6 +203,9 @@ extern "C" int eab_run_program(const eab_op* ops, int n_ops, eab_stream_t stream
             case EAB_OP_FS_BWD:
                 rc = eab_filter_sum_bwd_f32(EAB_P(0), EAB_P(1), EAB_W(2), o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], stream);
                 break;
+            case EAB_OP_INPUT_GRAD:
+                rc = eab_input_grad_f32(EAB_P(0), EAB_P(1), EAB_P(2), EAB_W(3), o.i[0], o.i[1], o.i[2], o.i[3], o.i[4], o.win.lens, stream);
+                break;
             case EAB_OP_LN_FWD:
                 rc = eab_layernorm64_fwd_f32(EAB_P(0), EAB_P(1), EAB_P(2), o.f[0], EAB_W(3), EAB_W(4), EAB_N64(0), stream);
                 break;

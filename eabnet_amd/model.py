@@ -312,6 +312,10 @@ class _HipModule(nn.Module):
         # of the smallest cap >= T (wider calls: of width T) -- one lowering and one pair of graphs per (B, cap) for every
         # narrower width and every combination of lengths.  EaBNet and GaGNet, is_causal=True, norm_type="IN"
         self.train_length_buckets = None
+        # gradient with respect to the input: False = an input that requires grad is refused, as always; True
+        # (EaBNet only) = such a call runs the training programs lowered with input_grad=True and x.grad arrives from
+        # loss.backward(); a call whose input needs no gradient runs the very program it ran before
+        self.input_grad = False
 
     def _param_fingerprint(self) -> tuple:
         """Change detector for the packed weights (runs on every forward).  Every parameter / buffer slot
@@ -459,17 +463,20 @@ class _HipModule(nn.Module):
             if not (all(x.is_cuda for x in inputs) and next(self.parameters()).is_cuda):
                 raise _lib.EabError(f"eabnet_amd.{name} trains on MI355X only: move the {noun} and the module to 'cuda'. "
                                     "There is no CPU fallback by design.")
+            x_leaf = None
             if any(x.requires_grad for x in inputs):
-                raise _refuse_differentiable(self, *self._input_grad_refusal)
+                if not (self.input_grad and self._has_input_grad):
+                    raise _refuse_differentiable(self, *self._input_grad_refusal)
+                x_leaf = inputs[0].to(torch.float32).contiguous()      # (stays in the caller's graph: the cast gives x.grad its dtype)
             if self.norm_type == "BN" and not self.training:
                 raise _refuse_differentiable(self, "BatchNorm in eval mode under autograd", "the training programs implement "
                                              "BatchNorm's train mode; call .train(), or torch.no_grad() for inference")
             lower = self._training_lowering()
             self.training_backend = "hip"
-            xs = tuple(x.detach().to(torch.float32).contiguous() for x in inputs)
+            xs = (x_leaf.detach(),) if x_leaf is not None else tuple(x.detach().to(torch.float32).contiguous() for x in inputs)
             if self.train_length_buckets is not None and vl is not None:
-                return train.forward_train(self, xs, lower, lengths=vl[1], cap=vl[0])
-            return train.forward_train(self, xs, lower, lengths=None if (vl is None or lengths is None) else vl[1])
+                return train.forward_train(self, xs, lower, lengths=vl[1], cap=vl[0], x_leaf=x_leaf)
+            return train.forward_train(self, xs, lower, lengths=None if (vl is None or lengths is None) else vl[1], x_leaf=x_leaf)
         if not all(x.is_cuda for x in inputs):
             raise _lib.EabError(f"eabnet_amd.{name} inference runs on MI355X only: move the {noun} (and module) to "
                                 "'cuda'. There is no CPU fallback by design.")
@@ -536,6 +543,8 @@ class _HipModule(nn.Module):
                                  f"(2 * {prog.history} + chunk)")
             return EaBNetStream(self, _Bound(prog, device), B, T_max, F, chunk, endless)
 
+    _has_input_grad = False      # the training lowering of this network takes input_grad=True (EaBNet)
+
     def _needs_graph(self, *inputs) -> bool:
         needs = torch.is_grad_enabled() and (any(x.requires_grad for x in inputs)
                                              or any(p.requires_grad for p in self.parameters()))
@@ -553,7 +562,8 @@ class EaBNet(_HipModule):
     backward as two static op programs behind one autograd node), so ``loss.backward()``, the optimiser,
     ``clip_grad_norm_`` and DistributedDataParallel work on the ordinary ``nn.Parameter``s.  CUDA
     tensors only; there is no second backend.  Refused (NotImplementedError): a gradient w.r.t. the input
-    spectrogram, BatchNorm in eval mode under autograd, more than 32 microphones.
+    spectrogram unless ``input_grad = True`` is set (then ``x.grad`` comes from the same programs),
+    BatchNorm in eval mode under autograd, more than 32 microphones.
     """
 
     def __init__(self, k1: tuple = (2, 3), k2: tuple = (1, 3), c: int = 64, M: int = 9, embed_dim: int = 64,
@@ -588,7 +598,8 @@ class EaBNet(_HipModule):
         return out.to(inpt.dtype)
 
     _input_grad_refusal = ("the input requires grad", "the training programs produce parameter gradients only, as the "
-                           "reference's training loop needs")
+                           "reference's training loop needs, unless the module's switch input_grad = True is set")
+    _has_input_grad = True
 
     def _training_lowering(self):
         from . import train
@@ -1183,31 +1194,94 @@ def stft_compress(wav: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor,
 
     lengths: optional (B,) sample counts, n_fft/2 < len <= L (a sequence or an integer tensor, host or device): utterance b
     is wav[b, :, :len[b]] and the rest of its rows is padding.  Its 1 + len[b] // hop frames are those of a call on that
-    utterance alone, bit for bit (the last frames reflect about ITS last sample); the frames after them are zeros."""
+    utterance alone, bit for bit (the last frames reflect about ITS last sample); the frames after them are zeros.
+
+    Differentiable: with grad enabled and ``wav.requires_grad`` the same launch runs inside an autograd node (the same bits)
+    whose backward is the adjoint kernel eab_stft_compress_bwd_f32 on the same window and lengths; the
+    gradient has the wave's dtype.  At a bin that is exactly zero -- a silent microphone, digital silence -- the compression
+    X |X|^-1/2 has an unbounded derivative and torch's own autograd returns NaN; this backward returns an exact (0, 0) there, so
+    the gradient of a wave with silent stretches stays finite.  More than 8 overlapping frames (ceil(n_fft / hop) > 8), or an
+    n_fft / 2 with a prime factor other than 2 and 5, are refused under autograd, as ``istft`` refuses them."""
     if lengths is not None:
         lengths = check_lengths(lengths, wav.shape[0], wav.shape[2], lo=n_fft // 2 + 1, unit="n_fft/2 < samples <= L", integral=True)
     if not wav.is_cuda:
         raise _lib.EabError("stft_compress needs a CUDA (ROCm) tensor; there is no CPU fallback by design.")
-    lib = _lib.load()
+    if torch.is_grad_enabled() and wav.requires_grad:
+        if hop > n_fft or -(-n_fft // hop) > 8:
+            raise NotImplementedError("stft_compress under autograd: the adjoint kernel implements any hop <= n_fft with at most 8 "
+                                      f"overlapping frames (ceil(n_fft / hop) in 1..8), got n_fft={n_fft}, hop={hop}; istft has "
+                                      "the same limit")
+        rest = n_fft // 2                             # (the factors of csrc/fft_lds.h: fft_plan)
+        for r in (5, 2):
+            while rest > 1 and rest % r == 0:
+                rest //= r
+        if n_fft % 2 or rest != 1:
+            raise NotImplementedError(f"stft_compress under autograd: n_fft={n_fft} -- the adjoint kernel runs its transform on the "
+                                      "LDS FFT, which needs an n_fft / 2 made of factors 2 and 5 (the forward's direct-DFT form has "
+                                      "no adjoint yet)")
+        return _StftCompress.apply(wav, _device_window(window, wav.device), lengths, n_fft, hop, layout)
+    x = wav.to(torch.float32).contiguous()
+    out = torch.empty(_stft_shape(x, n_fft, hop, layout), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        lens = None if lengths is None else _device_lengths(lengths, x.device)
+        _stft_launch(_lib.load(), x, _device_window(window, x.device), _twiddle(n_fft, x.device), out, lens, n_fft, hop, layout)
+    return out
+
+
+def _stft_shape(wav: torch.Tensor, n_fft: int, hop: int, layout: int) -> tuple:
     B, M, L = wav.shape
     T, F = 1 + L // hop, n_fft // 2 + 1
-    wav = wav.to(torch.float32).contiguous()
-    window = _device_window(window, wav.device)
-    out = torch.empty((B, T, F, M, 2) if layout == 0 else (B, 2, T, F), dtype=torch.float32, device=wav.device)
-    with torch.cuda.device(wav.device):
-        tw = _twiddle(n_fft, wav.device)
-        if lengths is not None:
-            lens = _device_lengths(lengths, wav.device)
-            _lib.check(lib.eab_stft_compress_lens_f32(wav.data_ptr(), window.data_ptr(), tw.data_ptr(), out.data_ptr(),
-                                                      lens.data_ptr(), B, M, L, n_fft, hop, layout,
-                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                       "eab_stft_compress_lens_f32")
-            return out
-        _lib.check(lib.eab_stft_compress_f32(wav.data_ptr(), window.data_ptr(), tw.data_ptr(), out.data_ptr(),
-                                             B, M, L, n_fft, hop, layout,
-                                             C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                   "eab_stft_compress_f32")
-    return out
+    return (B, T, F, M, 2) if layout == 0 else (B, 2, T, F)
+
+
+def _stft_launch(lib, wav: torch.Tensor, window: torch.Tensor, tw: torch.Tensor, out: torch.Tensor, lens, n_fft: int, hop: int,
+                 layout: int) -> None:
+    """the one forward launch of ``stft_compress``, with and without autograd: fp32 contiguous wav (B, M, L); lens: the device
+    sample counts or None"""
+    B, M, L = wav.shape
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if lens is not None:
+        _lib.check(lib.eab_stft_compress_lens_f32(wav.data_ptr(), window.data_ptr(), tw.data_ptr(), out.data_ptr(), lens.data_ptr(),
+                                                  B, M, L, n_fft, hop, layout, stream), "eab_stft_compress_lens_f32")
+    else:
+        _lib.check(lib.eab_stft_compress_f32(wav.data_ptr(), window.data_ptr(), tw.data_ptr(), out.data_ptr(), B, M, L, n_fft, hop,
+                                             layout, stream), "eab_stft_compress_f32")
+
+
+class _StftCompress(torch.autograd.Function):
+    """``stft_compress`` on a wave that requires grad: the forward is the launch ``stft_compress`` makes for any other input (the
+    same values), the backward the adjoint kernel eab_stft_compress_bwd_f32 at the saved output, on the same window and, where
+    given, the same lengths."""
+
+    @staticmethod
+    def forward(ctx, wav: torch.Tensor, window: torch.Tensor, lengths, n_fft: int, hop: int, layout: int) -> torch.Tensor:
+        lib = _lib.load()
+        x = wav.detach().to(torch.float32).contiguous()
+        out = torch.empty(_stft_shape(x, n_fft, hop, layout), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            tw = _twiddle(n_fft, x.device)
+            lens = None if lengths is None else _device_lengths(lengths, x.device)
+            _stft_launch(lib, x, window, tw, out, lens, n_fft, hop, layout)
+        ctx.save_for_backward(window, tw, out, *(() if lens is None else (lens,)))
+        ctx.geom = (tuple(x.shape), n_fft, hop, layout, wav.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, dspec):
+        window, tw, spec, *rest = ctx.saved_tensors
+        (B, M, L), n_fft, hop, layout, dtype = ctx.geom
+        lib = _lib.load()
+        g = dspec.detach().to(torch.float32).contiguous()
+        dwav = torch.empty((B, M, L), dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            rc = lib.eab_stft_compress_bwd_f32(g.data_ptr(), spec.data_ptr(), window.data_ptr(), tw.data_ptr(), dwav.data_ptr(),
+                                               rest[0].data_ptr() if rest else None, B, M, L, n_fft, hop, layout,
+                                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if rc == _lib.EAB_EUNSUPPORTED:
+            raise NotImplementedError(f"stft_compress under autograd: n_fft={n_fft}, hop={hop} -- the adjoint kernel needs hop <= "
+                                      "n_fft, at most 8 overlapping frames and an n_fft / 2 made of factors 2 and 5")
+        _lib.check(rc, "eab_stft_compress_bwd_f32")
+        return dwav.to(dtype), None, None, None, None, None
 
 
 _COPY_POOL = None

@@ -42,6 +42,7 @@ OP_WGRAD = 32            # train.WgradOp: weight gradient of a convolution
 OP_CLN_STATS, OP_CLN_APPLY, OP_GATE_ROWS = 33, 34, 35
 OP_GAG_CRM_BWD, OP_CLN_BWD = 36, 37
 OP_CLN_STEP = 38         # run-time only (runtime.fuse_step): statistics + apply of a cLN unit for a one-frame streaming step in one launch
+OP_INPUT_GRAD = 39       # training programs lowered with input_grad: eab_input_grad_f32 (csrc/input_grad.hip)
 NB_SUMS_ZEROED = 0x100   # mode-word flag of the norm backward: the caller has zero-filled the sums scratch
 NB_SUM_COPIES = 8        # the norm backward's reduce pass spreads its atomics over that many copies
 STORE_BF16 = 0x200       # mode-word flag: the op's output tensor is stored as bf16

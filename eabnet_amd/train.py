@@ -22,7 +22,12 @@ arena goes back to the flat gradient through the inverse table.
 
 Scope: every constructor branch of the reference (`supported`): U2 / plain U-Net, LSTM / cnn head, mimo / miso, cat / add,
 causal or not, InstanceNorm, BatchNorm (train mode) and cLN, up to 32 microphones.  This is the package's only differentiable
-path; what it does not cover (a gradient w.r.t. the input, eval-mode BatchNorm under autograd) is refused by model.py.
+path; what it does not cover (eval-mode BatchNorm under autograd) is refused by model.py.
+
+input_grad: the same programs plus the gradient with respect to the input -- the data gradient of the one
+convolution that reads it, padded to a 64-column tile, and ONE op (eab_input_grad_f32) that adds the filter-and-sum's adjoint
+with respect to X and writes the boundary buffer `din` (B, T, F, M, 2).  Every op of the programs without the switch keeps its
+place, name and operands; the added ops and their arena regions come last.
 """
 from __future__ import annotations
 
@@ -41,7 +46,7 @@ from . import program as prg
 from .runtime import BoundProgram
 from .program import ALIGN, EPS_IN, EPS_LN, Geometry, Ref, Stats, conv_tiles, pack_taps, unit_rows
 from .program import (NB_SUM_COPIES, NB_SUMS_ZEROED, OP_ADD, OP_CLN_BWD, OP_COLSUM, OP_FILTER_SUM, OP_FS_BWD, OP_GATE_BWD,  # noqa: F401
-                      OP_GATE_FWD, OP_GATHER, OP_GLU_BWD, OP_IN_STATS, OP_LN_BWD, OP_LN_FWD, OP_LSTM_BWD, OP_LSTM_TRAIN,
+                      OP_GATE_FWD, OP_GATHER, OP_GLU_BWD, OP_IN_STATS, OP_INPUT_GRAD, OP_LN_BWD, OP_LN_FWD, OP_LSTM_BWD, OP_LSTM_TRAIN,
                       OP_NORM_BWD, OP_RELU_BWD, OP_TR_NORM_ACT, OP_WGRAD, STORE_BF16, XF_NORM_PRELU, XF_PRELU_NORM)
 from .spec import NetConfig, gate_key, param_specs
 
@@ -166,7 +171,8 @@ class TrainLowering:
     spec_fn = staticmethod(param_specs)              # parameter inventory of the network being lowered (subclasses: GaGNet)
     supports = staticmethod(supported)
 
-    def __init__(self, cfg, B: int, T: int, F: int = 161, precision: str = "f32"):
+    def __init__(self, cfg, B: int, T: int, F: int = 161, precision: str = "f32", input_grad: bool = False):
+        self.input_grad = bool(input_grad)
         if precision not in ("f32", "bf16"):
             raise ValueError("training precision is 'f32' or 'bf16' (bf16: forward, dgrad and wgrad contractions on the bf16 "
                              "matrix cores with fp32 accumulation -- the LSTM's recurrent products included; cell state, norms, "
@@ -218,6 +224,8 @@ class TrainLowering:
         self.flops_bwd = 0
         self.emit = self.fwd                                                  # the list ops are appended to
         self.gtaps: Dict[str, TVar] = {}                                      # named activations whose gradient tests read back
+        self.din_tile: Optional[TVar] = None                                  # input_grad: the input's gradient through its convolution
+        self.bf_w: Optional[TVar] = None                                      # the beam-forming weight rows of the forward
 
     def mark(self, which: str, what: str, lanes: Sequence[int]) -> None:
         """fork / join of parallel branches in front of the next op of the forward or backward list (executed by TrainBound.run
@@ -484,6 +492,16 @@ class TrainLowering:
                 wd = np.ascontiguousarray(wn[:, c_lo:c_lo + s.C].transpose(1, 0, 2))      # (C_s, N packed, kt * kf)
                 self.dgrad(f"{name}.dgrad", s, dz, [(self.wadd(f"{wkey}.wd.{c_lo}" + ("" if transposed else f".{g.ophase}"),
                                                                pack_taps(wd, g.taps)), g) for g in Geometry.adjoint(geoms)], N=N)
+                if s.ref.arena == "in" and self.input_grad:
+                    # the gradient of the network input: the same launches with the transposed weights padded to
+                    # one 64-column tile (index -1 = a zero weight in the pad rows, as w2 of the head), into a [rows][64] scratch
+                    # in memory-channel order m*2+ri that eab_input_grad_f32 gathers
+                    assert not transposed and len(srcs) == 1 and self.din_tile is None and s.C <= MLP_LD
+                    wd64 = np.full((MLP_LD,) + wd.shape[1:], -1, np.int64)
+                    wd64[:s.C] = wd
+                    self.din_tile = TVar(s.ref, s.F, MLP_LD, Slot())
+                    self.dgrad(f"{name}.dgrad_in", self.din_tile, dz,
+                               [(self.wadd(f"{wkey}.wd64.{g.ophase}", pack_taps(wd64, g.taps)), g) for g in Geometry.adjoint(geoms)], N=N)
                 c_lo += s.C
         self.tape.append(back)          # before the norm/PReLU closure on the tape = after it in the backward
         if self.cln and norm:
@@ -723,7 +741,7 @@ class TrainLowering:
             self.conv_op("bf_map", [e], self.wadd("bf_map.w", wcimg), self.wadd("bf_map.b", bcimg), pw, N=MLP_LD, epi=prg.EPI_LINEAR,
                          dst=bw.ref)
             self.fwd.append(GenOp(OP_FILTER_SUM, [bw.ref, Ref("in"), Ref("out")], [B, T, F, M, MLP_LD], name="filter_sum"))
-            self.gtaps["bf_w"] = bw
+            self.gtaps["bf_w"] = self.bf_w = bw
 
             def back_head_cnn():
                 dbw = self.alloc(rows * MLP_LD)
@@ -769,7 +787,7 @@ class TrainLowering:
                      epi=prg.EPI_LINEAR, dst=bw.ref)
         self.fwd.append(GenOp(OP_FILTER_SUM, [bw.ref, Ref("in"), Ref("out")], [B, T, F, M, MLP_LD], name="filter_sum"))
 
-        self.gtaps["bf_w"] = bw
+        self.gtaps["bf_w"] = self.bf_w = bw
         self.gtaps["bf_map.ln"] = x_ln
         self.gtaps["bf_map.y1"] = y1
 
@@ -810,6 +828,11 @@ class TrainLowering:
         # ---- backward: replay the tape in reverse
         for fn in reversed(self.tape):
             fn()
+        if self.input_grad:
+            # din = the filter-and-sum's adjoint w.r.t. X + the first convolution's data gradient, one launch (csrc/input_grad.hip)
+            assert self.din_tile is not None and self.bf_w is not None, "no convolution read the network input"
+            self.bwd.append(GenOp(OP_INPUT_GRAD, [Ref("dout"), self.bf_w.ref, self.grad_of(self.din_tile), Ref("din")],
+                                  [self.B, self.T, self.F, self.cfg.M, MLP_LD], name="input_grad"))
         return self.finish()
 
     def assign_bf16_storage(self) -> None:
@@ -925,7 +948,7 @@ class TrainLowering:
                             flops_fwd=self.flops_fwd, flops_bwd=self.flops_bwd,
                             grad_taps={k: (v.slot.ref, v.F, v.C) for k, v in self.gtaps.items() if v.slot.ref is not None},
                             lanes={"fwd": [o.lane for o in self.fwd], "bwd": [o.lane for o in self.bwd]}, sync=self.sync,
-                            bn_layers=list(self.bn_layers))
+                            bn_layers=list(self.bn_layers), input_grad=self.input_grad)
 
 
 @dataclass
@@ -956,12 +979,13 @@ class TrainProgram:
     bn_layers: List[tuple] = field(default_factory=list)
     varlen: bool = False                     # the ops that sum or recurse across rows read per-utterance lengths (flag_varlen)
     bucket: bool = False                     # T is a cap serving every call of T frames or fewer (train_length_buckets)
+    input_grad: bool = False                 # the backward list also writes the boundary buffer 'din' (B, T, F, M, 2)
 
 
 # op kinds that honour eab_op.win.lens in the training programs, with the i[] slots that carry (B, T) where the op has none
 # (written by runtime.encode only together with the lengths pointer); the convolutions carry lens in their own descriptor
 VARLEN_KINDS = {OP_IN_STATS: ("T", 4), OP_NORM_BWD: ("T", 5), OP_LN_BWD: ("BT", 2), OP_LSTM_BWD: None, OP_FILTER_SUM: None,
-                OP_WGRAD: None, prg.OP_GAG_CRM_BWD: None}
+                OP_WGRAD: None, prg.OP_GAG_CRM_BWD: None, OP_INPUT_GRAD: None}
 # (the post-filter's GAG_PACK and GAG_CRM are prg.GagPackOp / GagCrmOp: they have a `win` attribute of their own and honour lens)
 # the length-bucket form also bounds the two LSTM recurrences by the longest length of a workgroup: the forward
 # takes the pointer, the backward a flag in i[4] (written, like every lens_i slot, only together with the pointer)
@@ -1005,13 +1029,14 @@ def varlen_unsupported_reason(cfg) -> str:
 
 
 def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "f32", varlen: bool = False,
-                bucket: bool = False, lstm_bound: bool = True) -> TrainProgram:
+                bucket: bool = False, lstm_bound: bool = True, input_grad: bool = False) -> TrainProgram:
     """varlen: the same op list with the cross-row readers flagged for per-utterance lengths (flag_varlen); T is the padded
     width.  bucket: the same with T a cap (the LSTM recurrences flagged too).  Configurations outside is_causal=True /
-    norm_type='IN' are refused."""
+    norm_type='IN' are refused.  input_grad: the backward list also produces the gradient of the input in the boundary buffer
+    'din' (see the module docstring); False is the program as it always was."""
     if (varlen or bucket) and varlen_unsupported_reason(cfg):
         raise NotImplementedError("training with per-utterance lengths: " + varlen_unsupported_reason(cfg))
-    prog = TrainLowering(cfg, B, T, F, precision).build()
+    prog = TrainLowering(cfg, B, T, F, precision, input_grad=input_grad).build()
     return flag_varlen(prog, bucket, lstm_bound) if (varlen or bucket) else prog
 
 
@@ -1020,7 +1045,7 @@ def lower_train(cfg: NetConfig, B: int, T: int, F: int = 161, precision: str = "
 # ----------------------------------------------------------------------------------------------------------------
 class TrainBound(BoundProgram):
     """Device arenas + the forward ("fwd") and backward ("bwd") op lists of a lowered training program."""
-    BOUNDARY = ("in", "out", "dout", "in2")
+    BOUNDARY = ("in", "out", "dout", "in2", "din")
 
     def __init__(self, prog: TrainProgram, device: torch.device):
         self.prog = prog
@@ -1100,7 +1125,8 @@ class TrainFn(torch.autograd.Function):
         tax = 1 if x.ndim == 5 else 2
         Tc = ctx.Tc = x.shape[tax]
         wide = lambda t: None if t is None else tuple(t.shape[:tax]) + (prog.T,) + tuple(t.shape[tax + 1:])  # noqa: E731
-        if bound.use_graph and bound.capture(wide(x), out_shape, out_shape, wide(x2)):
+        din_shape = wide(x) if prog.input_grad else None        # the input's gradient: a boundary buffer of the backward list
+        if bound.use_graph and bound.capture(wide(x), out_shape, out_shape, wide(x2), din_shape):
             if Tc == prog.T:
                 bound.static["in"].copy_(x)
                 if x2 is not None:
@@ -1122,7 +1148,7 @@ class TrainFn(torch.autograd.Function):
                     x2w.narrow(tax, 0, Tc).copy_(x2)
                     x2 = x2w
             out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-            ctx.io = (x, out, torch.empty_like(out), x2)
+            ctx.io = (x, out, torch.empty_like(out), x2, None if din_shape is None else x.new_empty(din_shape))
             bound.bind(*(None if t is None else t.data_ptr() for t in ctx.io))
             bound.run("fwd", st)
             if Tc != prog.T:
@@ -1150,7 +1176,26 @@ class TrainFn(torch.autograd.Function):
         gflat = torch.empty(prog.n_params, dtype=torch.float32, device=bound.device)     # fresh per call: .grad may keep views of it
         bound.unpack_grads(gflat, st)
         grads = finish_flat_gradient(gflat, ctx.sync_group, ctx.shapes, ctx.dtypes, ctx.needs_input_grad[3:])
+        ctx.din = None
+        if prog.input_grad:                                            # (a fresh tensor per call: .grad may keep it)
+            din = bound.static["din"] if ctx.io is None else ctx.io[4]
+            ctx.din = din.narrow(1, 0, ctx.Tc).clone() if (ctx.io is None or ctx.Tc != prog.T) else din
         return (None, None, None, *grads)
+
+
+class TrainInputFn(TrainFn):
+    """TrainFn for a program lowered with input_grad: the network input is an argument of the node, and the backward returns
+    the boundary buffer `din`, narrowed to the call's width, as its gradient.  ``x`` is fp32 and contiguous."""
+
+    @staticmethod
+    def forward(ctx, bound: TrainBound, sync_group, x: torch.Tensor, *params: torch.Tensor) -> torch.Tensor:
+        assert bound.prog.input_grad
+        return TrainFn.forward(ctx, bound, sync_group, (x.detach(),), *params)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        _, _, _, *grads = TrainFn.backward(ctx, grad_out)
+        return (None, None, ctx.din, *grads)
 
 
 def flat_parameter_view(params) -> Optional[torch.Tensor]:
@@ -1188,14 +1233,16 @@ def finish_flat_gradient(gflat: torch.Tensor, sync_group, shapes, dtypes, needs)
     return grads
 
 
-def forward_train(module, inputs: tuple, lower, lengths=None, cap: Optional[int] = None) -> torch.Tensor:
+def forward_train(module, inputs: tuple, lower, lengths=None, cap: Optional[int] = None, x_leaf: Optional[torch.Tensor] = None) -> torch.Tensor:
     """A differentiable forward of ``module`` on its HIP training programs, lowered by ``lower(cfg, B, T, F, precision)``
     (lower_train here, train_gag.lower_train for GaGNet).  ``inputs``: fp32, contiguous, (B, T, F, M, 2) for EaBNet or two
     (B, 2, T, F) for GaGNet.  Returns the program's output arena ((B, 2, T, F), or (q, B, 2, T, F) for GaGNet).
     ``lengths`` (checked by model.check_lengths: a list or a device tensor of B frame counts): the program lowered with
     varlen=True, its lengths array written on the current stream before the forward replay -- no host synchronisation.
     ``cap`` (train_length_buckets, DESIGN §4.27): the program lowered with bucket=True at width ``cap`` >= T serves the call;
-    ``lengths`` is then a list, a device tensor or one int for every utterance; returned tensors have the call's width T."""
+    ``lengths`` is then a list, a device tensor or one int for every utterance; returned tensors have the call's width T.
+    ``x_leaf`` (EaBNet.input_grad): inputs[0] as a tensor of the caller's graph, fp32 and contiguous -- the program is lowered
+    with input_grad=True and the node hands the gradient of the input back to it."""
     _lib.load()
     x = inputs[0]
     B, T, F = (x.shape[0], x.shape[1], x.shape[2]) if x.ndim == 5 else (x.shape[0], x.shape[2], x.shape[3])
@@ -1209,6 +1256,10 @@ def forward_train(module, inputs: tuple, lower, lengths=None, cap: Optional[int]
     # (module.train_bucket_lstm_bound = False, a measurement switch: the bucket program with both LSTM recurrences walking the cap)
     lstm_bound = bool(getattr(module, "train_bucket_lstm_bound", True))
     key = (B, Tp, F, str(x.device), prec, varlen) + (((True,) if lstm_bound else ("lstm_walks_cap", True)) if bucket else ())
+    ig = x_leaf is not None
+    if ig:                                             # (the other keys keep their form)
+        key += ("input_grad",)
+        lower = functools.partial(lower, input_grad=True)
     bound = cache.pop(key, None)
     if bound is None:
         # a small LRU of bound programs (variable-length batches, a smaller last batch, alternating train / validation
@@ -1233,7 +1284,7 @@ def forward_train(module, inputs: tuple, lower, lengths=None, cap: Optional[int]
                 bound.lens.copy_(lengths.to(torch.int32), non_blocking=True)
             else:
                 bound.lens.copy_(torch.as_tensor(lengths, dtype=torch.int32).pin_memory(), non_blocking=True)
-        out = TrainFn.apply(bound, sync, inputs, *params)
+        out = TrainInputFn.apply(bound, sync, x_leaf, *params) if ig else TrainFn.apply(bound, sync, inputs, *params)
         bound.update_bn_buffers(module)
     return out
 

@@ -1099,6 +1099,34 @@ int eab_cln_step_f32(const float* x, const float* stat_slope, double* sums, doub
 #define EAB_OP_CLN_STEP 38  /* eab_cln_step_f32: p = {x, stat_slope, sums, state, mr, gain, bias, slope, add, y}, i = {B, T, P, C, mode}, f = {eps} */
 #define EAB_OP_CLN_BWD 37   /* eab_train_cln_bwd_f32: p = {dy, x, mr, gain, bias, slope, rowsums, ab, part, acc_in, dx}, i = {B, T, P, C, mode} */
 
+/* --------------------------------------------------------------------------
+ * Input gradients
+ *   eab_input_grad_f32: the gradient of the training programs with respect to the network input x [B][T][F][M][2], one launch
+ *     that stores every element of din once.  dout [B][2][T][F] planar; bw [B][T][F][ld], the beam-forming weights of the
+ *     forward (first 2M columns, pairs (re, im) per microphone); dconv [B][T][F][ld], the data gradient of the first
+ *     convolution in memory-channel order m*2+ri (columns >= 2M are not read):
+ *       din[bin][m].re = dr w.re + di w.im + dconv[bin][2m]
+ *       din[bin][m].im = di w.re - dr w.im + dconv[bin][2m+1]
+ *     -- the filter-and-sum's adjoint with respect to x (eab_filter_sum_bwd_f32 with its operands exchanged) fused into the
+ *     gather of the convolution's gradient.  lens != NULL (device, B frame counts): frames t >= lens[b] are stored as exact
+ *     zeros by selection, whatever the operands hold there.
+ *   eab_stft_compress_bwd_f32: the adjoint of eab_stft_compress_f32 / eab_stft_compress_lens_f32.  dspec and spec (the
+ *     forward's stored output) in `layout`, window and twiddle as the forward's; dwav [B][M][L].  Per bin, with s the stored
+ *     value, rho = |s| and g the incoming gradient: gX = g / rho - s (s . g) / (2 rho^3), exactly (0, 0) at rho = 0 (no division;
+ *     the true derivative is unbounded there); then the plain transpose of the one-sided windowed DFT (interior bins not
+ *     doubled, the imaginary parts at DC and Nyquist dropped), the overlap sum over the frames t < 1 + L_b / hop and the fold
+ *     of the reflected margins back onto the samples.  lens (NULL: every utterance L samples): the forward's sample counts,
+ *     clamped as there; samples j >= lens[b] are zeros and frames behind an utterance are never read.  No atomics, one store
+ *     per sample, the same bits alone and in any batch.  EAB_EUNSUPPORTED: more than 8 frames cover a sample
+ *     (ceil(n_fft / hop) > 8, as eab_istft_f32), hop > n_fft, or n_fft / 2 has a prime factor other than 2 and 5.
+ *   program op INPUT_GRAD:  p = {dout, bw, dconv, din}   i = {B, T, F, M, ld}   (win.lens honoured)
+ * ------------------------------------------------------------------------ */
+int eab_input_grad_f32(const float* dout, const float* bw, const float* dconv, float* din, int B, int T, int F, int M, int ld,
+                       const int32_t* lens, eab_stream_t stream);
+int eab_stft_compress_bwd_f32(const float* dspec, const float* spec, const float* window, const float* twiddle, float* dwav,
+                              const int32_t* lens, int B, int M, int L, int n_fft, int hop, int layout, eab_stream_t stream);
+#define EAB_OP_INPUT_GRAD 39
+
 /* struct-layout handshake for foreign-function mirrors of the structs above */
 int eab_sizeof_conv_desc(void);
 int eab_sizeof_op(void);
