@@ -29,6 +29,9 @@ from dataclasses import dataclass
 from typing import Tuple
 
 
+MAX_MICS = 32     # BFW_MAXM of csrc/filter_sum.hip
+
+
 @dataclass(frozen=True)
 class NetConfig:
     """Hyper-parameters of EaBNet.__init__ (reference EaBNet.py:10-27)."""
@@ -56,11 +59,24 @@ class NetConfig:
     c_end: int = 64
     hid_node: int = 64
 
+    def __post_init__(self) -> None:
+        self._check_mics()
+
+    def _check_mics(self) -> None:
+        """The beam-forming head (eab_mlp_bfw_filter_sum_f32, every bf_type and topo_type) keeps the 2M weights of a bin in
+        one 64-wide tile row and refuses M > 32 (BFW_MAXM, csrc/filter_sum.hip); without this the network would lower and
+        bind and fail at its first launch with a bare argument error."""
+        if self.M > MAX_MICS:
+            raise NotImplementedError(
+                f"eabnet_amd: M={self.M} microphones; the beam-forming kernel holds at most M={MAX_MICS} per bin "
+                "(BFW_MAXM, csrc/filter_sum.hip)")
+
     def check_supported(self) -> None:
         """Every switch of the reference constructor is implemented (U2/plain U-Net, lstm/cnn
         beam-former, mimo/miso, cat/add, IN/BN, causal or not) and the time extent of the gated convolutions
         (k1 = (1..5, 3)).  The rest of the kernel geometry (64-channel layers, 3-bin kernels, (1,3) units) is fixed; ``cLN`` cannot be constructed in the reference
         either (EaBNet.py:689-691 pass the string dim_size as num_features)."""
+        self._check_mics()
         bad = []
         if self.bf_type not in ("lstm", "cnn"):
             bad.append(f"bf_type={self.bf_type!r}")
